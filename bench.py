@@ -9,10 +9,20 @@ them with no data-path collective (weak scaling); the only collectives are the t
 and the max-over-ranks of the elapsed time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--fields F] [--mode full|sa|cma|dma]
+                    [--dump-outputs DIR] [--full]
 
 Rank 0 prints ONE JSON line (value = env-steps/s summed over all ranks = fields x ranks x K /
-max-over-ranks time).  `roofline.achieved` = algorithmic bytes per launch / mean launch time
-measured with HIP events on the launch stream; `cpu_baseline` = the C oracle (oracle/, the only
+max-over-ranks time; `ms_per_step` = the wall time of one timed step).  `roofline.achieved` =
+algorithmic bytes per launch / mean launch time measured with HIP events on the launch stream.
+
+A plain run does only what that headline needs: set-up, W warm-up steps, the K timed steps, the
+outputs of the last timed step written to DIR if `--dump-outputs DIR` is given (rank 0's
+`DIR/<name>.npy`, float32, a fixed seeded sample of 8,192 rows of every array longer than that; the
+inputs are seeded, so two builds run with the same arguments can be compared array for array), and
+the result line.  Every further measurement runs only with `--full`, where the options that size or
+skip the legs (`--ppo-updates`, `--rollout-k`, `--no-cpu-baseline`, ...) apply: the per-launch event
+pass, the past-L3, rollout and SA legs, the PPO-SA / PPO-DMA train loops, the update GEMM's roofline
+and the CPU baseline.  `cpu_baseline` = the C oracle (oracle/, the only
 use of it here) on the host's cores (one 4,096-field shard per thread, up to 16: 65,536 fields on a 16-core share) over a bounded
 sample, with one-thread rates at the SURVEY §8(d) shapes (16 fields x 1,000 steps = config 1,
 4,096 and 65,536 fields) beside it.  `past_l3` repeats the FULL timing at 131,072 fields, whose
@@ -69,6 +79,11 @@ def parse():
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--fields", type=int, default=65536, help="fields (3v3 matches) per GPU")
     p.add_argument("--mode", default="full", choices=["full", "sa", "cma", "dma"])
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every further leg (per-launch events, past-L3, rollout, SA, PPO-SA / PPO-DMA, update "
+                        "GEMM roofline, CPU baseline); the options below size or skip those legs and matter only here")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--rollout-k", type=int, default=16,
@@ -446,6 +461,21 @@ def update_gemm_roofline(dev, rows: int = 2097152, reps: int = 10) -> dict:
             "fp32_mfma_peak": peak_fp32, "vs_fp32_mfma_peak": tf / peak_fp32, "kernel_ms": ms}
 
 
+DUMP_ROWS = 8192  # rows kept of each dumped array (all of it if shorter): ~23 MB in all for the FULL contract
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """`arrays`: name -> tensor with one row per field / agent row.  Writes path/<name>.npy in float32;
+    an array of more than DUMP_ROWS rows is cut to a fixed (seeded) sorted sample of its rows."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        rows = t.shape[0]
+        if rows > DUMP_ROWS:
+            idx = np.sort(np.random.default_rng(0).choice(rows, DUMP_ROWS, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.to(torch.float32).cpu().numpy())
+
+
 def reduce_max(values, device="cpu"):
     """Max over ranks of the per-rank timings (the only cross-rank data besides barriers)."""
     t = torch.tensor(values, dtype=torch.float64, device=device)
@@ -570,16 +600,26 @@ def main():
     elapsed = time.perf_counter() - t0
     region_ms = r0.elapsed_time(r1) / args.steps
 
-    # ---- diagnostic: per-launch HIP events (a separate pass of the same launches; each event
+    # ---- what the last timed step computed, as its caller receives it (and the state it left), copied
+    # to files before any further leg launches on these buffers ----
+    if args.dump_outputs and rank == 0:
+        arrays = {k: io[k] for k in ("obs", "terminal_obs", "rew", "reward_sum", "dones_rep", "time_outs", "progress_f")
+                  if io.get(k) is not None}
+        arrays.update(dones=env.reset_buf, progress=env.progress_buf, state=env.state.t())
+        dump_outputs(args.dump_outputs, arrays)
+
+    # ---- diagnostic (--full): per-launch HIP events (a separate pass of the same launches; each event
     # pair adds its own overhead, so this reads ~2-3 % above the region average) ----
-    n_ev = min(args.steps, 100)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
-    for k in range(n_ev):
-        ev[k][0].record()
-        launch(k)
-        ev[k][1].record()
-    torch.cuda.synchronize()
-    per_launch_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    per_launch_ms = 0.0
+    if args.full:
+        n_ev = min(args.steps, 100)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
+        for k in range(n_ev):
+            ev[k][0].record()
+            launch(k)
+            ev[k][1].record()
+        torch.cuda.synchronize()
+        per_launch_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
     elapsed, kern_ms, per_launch_ms = reduce_max([elapsed, region_ms, per_launch_ms],
                                                  dev if args.dist_backend == "nccl" else "cpu")
@@ -590,7 +630,7 @@ def main():
     ppo_updates = args.ppo_updates if args.ppo_updates is not None else ppo_updates_to_1e8(n, world)
     if args.share_gpu:
         os.environ["VSS_LOCAL_DEVICE"] = "0"
-    if ppo_updates > 0:
+    if args.full and ppo_updates > 0:
         if world > 1:
             dist.barrier()
         ppo = ppo_wallclock(n, ppo_updates, dev, world)
@@ -598,7 +638,7 @@ def main():
         torch.cuda.empty_cache()
         if rank == 0:
             ppo["update_gemm_roofline"] = update_gemm_roofline(dev)
-    if args.ppo_dma_updates > 0:
+    if args.full and args.ppo_dma_updates > 0:
         if world > 1:
             dist.barrier()
         ppo_dma = ppo_dma_leg(n, args.ppo_dma_updates, dev, world)
@@ -646,20 +686,21 @@ def main():
                        "parallelism": f"fields sharded over {world} GPU(s), no data-path collective"},
             "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK, "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": algo, "kernel_ms": kern_ms,
-                         "kernel_ms_per_launch_events": per_launch_ms},
+                         "algorithmic_bytes_per_launch": algo, "kernel_ms": kern_ms},
         }
-        if args.l3_check_fields > 0 and mode == N.MODE_FULL:
+        if args.full:
+            out["roofline"]["kernel_ms_per_launch_events"] = per_launch_ms
+        if args.full and args.l3_check_fields > 0 and mode == N.MODE_FULL:
             out["past_l3"] = past_l3_leg(args.l3_check_fields, args.steps, dev)
-        if args.rollout_k > 0 and mode == N.MODE_FULL:
+        if args.full and args.rollout_k > 0 and mode == N.MODE_FULL:
             out["rollout"] = rollout_leg(env, args.rollout_k, args.steps, gen, dev)
-        if mode == N.MODE_FULL:
+        if args.full and mode == N.MODE_FULL:
             out["sa_step"] = sa_leg(env, args.steps, gen, dev)
         if ppo is not None:
             out["ppo"] = ppo
         if ppo_dma is not None:
             out["ppo_dma"] = ppo_dma
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if world > 1:

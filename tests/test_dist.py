@@ -54,7 +54,7 @@ def test_bench_two_ranks_rehearsal(launcher):
            "--master-addr", "127.0.0.1", "--master-port", str(port)] if launcher == "torchrun" else [sys.executable]
     cmd = run + [os.path.join(REPO, "bench.py"),
                  "--gpus", "2", "--steps", "20", "--warmup", "2", "--fields", "8192", "--dist-backend", "gloo",
-                 "--share-gpu", "--no-cpu-baseline",
+                 "--share-gpu", "--full", "--no-cpu-baseline",
                  "--ppo-updates", "1", "--rollout-k", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]

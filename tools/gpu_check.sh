@@ -27,24 +27,24 @@ STEPS=${STEPS:-tests,smoke,bench,prof}
 case ",$STEPS," in *,tests,*) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;; esac
 case ",$STEPS," in *,tplay,*) run pytest_play 600 python -m pytest tests/test_play.py -m gpu -x -q ;; esac
 case ",$STEPS," in *,smoke,*) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;; esac
-case ",$STEPS," in *,bench,*) run bench 400 python bench.py; run bench_eager 300 python bench.py --graph 0 --no-cpu-baseline ;; esac
-case ",$STEPS," in *,benchsa,*) run bench_sa 300 python bench.py --mode sa --no-cpu-baseline ;; esac
+case ",$STEPS," in *,bench,*) run bench 400 python bench.py --full; run bench_eager 300 python bench.py --full --graph 0 --no-cpu-baseline ;; esac
+case ",$STEPS," in *,benchsa,*) run bench_sa 300 python bench.py --full --mode sa --no-cpu-baseline ;; esac
 case ",$STEPS," in *,prof,*)
   run rocprof_stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o run -- \
-      python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --l3-check-fields 0 ;;
+      python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --l3-check-fields 0 ;;
 esac
 case ",$STEPS," in *,pmc,*)
   run rocprof_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_$TAG" -o run -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0
   run rocprof_write 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_$TAG" -o run -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0 ;;
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0 ;;
 esac
 # the same two passes at 131,072 fields (406 MB per launch, past the 256 MiB Infinity Cache)
 case ",$STEPS," in *,pmcl3,*)
   run rocprof_fetch_l3 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_l3_$TAG" -o run -- \
-      python3 bench.py --fields 131072 --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0
+      python3 bench.py --full --fields 131072 --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0
   run rocprof_write_l3 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_l3_$TAG" -o run -- \
-      python3 bench.py --fields 131072 --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0 ;;
+      python3 bench.py --full --fields 131072 --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --l3-check-fields 0 --rollout-k 0 ;;
 esac
 case ",$STEPS," in *,tupd,*) run pytest_update 600 python -u -m pytest tests/test_update.py tests/test_ppo.py tests/test_policy.py -m gpu -x -v --timeout 200 --timeout-method thread ;; esac
 # the update's fused-epilogue GEMMs: unit tests, kernel bench vs torch, PPO update fused vs split
@@ -73,26 +73,26 @@ case ",$STEPS," in *,ppo1e8,*)
       --total-timesteps 100663296 --save-path "$OUT/runs_$TAG" && \
   run ppo_dma 900 python rsoccer-isaac-cleanrl_amd/ppo_continuous_action_isaacgym.py --env-id dma --num-envs 196608 \
       --num-updates 2 --save-path "$OUT/runs_$TAG" && \
-  run bench_dma 300 python bench.py --mode dma --no-cpu-baseline --ppo-updates 0 ;; esac
+  run bench_dma 300 python bench.py --full --mode dma --no-cpu-baseline --ppo-updates 0 ;; esac
 case ",$STEPS," in *,sq,*)
   run rocprof_sq 400 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --output-format csv -d "$OUT/pmc_sq_$TAG" -o run -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   run rocprof_sq2 400 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM_WR SQ_INSTS_SMEM GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_sq2_$TAG" -o run -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline ;;
 esac
 case ",$STEPS," in *,profall,*)
   run prof_full 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o run -- \
-      python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --ppo-updates 0 --rollout-k 16
+      python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --ppo-updates 0 --rollout-k 16
   run prof_sa 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_sa_$TAG" -o run -- \
-      python3 bench.py --mode sa --steps 100 --warmup 10 --no-cpu-baseline --ppo-updates 0
+      python3 bench.py --full --mode sa --steps 100 --warmup 10 --no-cpu-baseline --ppo-updates 0
   run pmc_fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_$TAG" -o run -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --rollout-k 0
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --rollout-k 0
   run pmc_write 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_$TAG" -o run -- \
-      python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --rollout-k 0
+      python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0 --rollout-k 0
   run pmc_fetch_sa 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_sa_$TAG" -o run -- \
-      python3 bench.py --mode sa --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0
+      python3 bench.py --full --mode sa --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0
   run pmc_write_sa 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_sa_$TAG" -o run -- \
-      python3 bench.py --mode sa --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0
+      python3 bench.py --full --mode sa --steps 20 --warmup 5 --no-cpu-baseline --ppo-updates 0
   run prof_policy 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_policy_$TAG" -o run -- \
       python3 tools/policy_bench.py
   run pmc_policy 400 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_MFMA SQ_WAVES SQ_BUSY_CYCLES --output-format csv -d "$OUT/pmc_policy_$TAG" -o run -- \
