@@ -182,6 +182,30 @@ int vss_step_replay(void* stream, int64_t n_fields, int32_t mode, const vss_para
                     const vss_state* st, const vss_step_io* io, const vss_replay_draws* draws);
 
 /*
+ * The yellow team's side of vss_step_versus (N = n_fields):
+ *   opp_actions  (N,3,2) actions of yellow robots 0..2; 8-B aligned                     read
+ *   opp_obs      (N,3,52) the yellow robots' observations AFTER the step's reset
+ *                (= rows [:,1] of FULL's obs); 16-B aligned                             write
+ */
+typedef struct vss_versus_io {
+  const float* opp_actions;
+  float* opp_obs;
+} vss_versus_io;
+
+/*
+ * vss_step in mode SA / CMA / DMA with the yellow team driven by `vs->opp_actions` (a policy's
+ * actions: a snapshot of the learner, a checkpoint, a scripted team) instead of the OU process.
+ * Every vss_step_io output keeps the meaning it has in vss_step for that mode.  Action slots: the
+ * learner's from io->actions, yellow's (6..11) from opp_actions; in SA blue robots 1-2 (slots 2..5)
+ * keep their OU update with the values vss_step(SA) would draw (same Philox counter, same
+ * operations); CMA and DMA draw no OU noise.  ou_buf afterwards holds all twelve applied, pre-clamp
+ * actions (zeroed for finished fields); rng_counter advances by 1.  The opponent does not learn, so
+ * it gets no terminal observation.  FULL takes all twelve actions itself: VSS_E_ARG.
+ */
+int vss_step_versus(void* stream, int64_t n_fields, int32_t mode, const vss_params* params,
+                    const vss_state* st, const vss_step_io* io, const vss_versus_io* vs);
+
+/*
  * K consecutive FULL-mode steps in one launch for a pre-supplied action sequence (random-action
  * benchmarks, scripted / OU opponents, evaluation): bit-identical to K vss_step(FULL) calls — the
  * same reference semantics per step (envs/vss.py:180-333) — with the field state kept on chip
@@ -249,6 +273,15 @@ int vss_value_forward_masked(void* stream, int64_t rows, int32_t n_act, const fl
                              uint64_t seed, uint64_t counter, const float* action_in, float* action_out,
                              float* logprob_out, float* entropy_out, float* value_out, float* mean_out,
                              const int64_t* row_mask);
+
+/*
+ * The actor alone (an opponent policy needs actions, not values): mean = actor(obs), action = mean +
+ * exp(logstd) * N(0,1) with the Philox stream and sampling formula of vss_policy_forward -- for equal
+ * (seed, counter, row) the sampled action is the same.  No critic is evaluated.  action_out / mean_out
+ * (rows, n_act); either may be NULL.
+ */
+int vss_actor_forward(void* stream, int64_t rows, int32_t n_act, const float* obs, const float* actor_packed,
+                      const float* logstd, uint64_t seed, uint64_t counter, float* action_out, float* mean_out);
 
 /*
  * The actor tail of Agent.get_action_and_value (ppo_continuous_action_isaacgym.py:157-164) from

@@ -577,6 +577,14 @@ __global__ __launch_bounds__(kWaves * 64, 2) void policy_split_kernel(PolicyArgs
   else split_body<NACT, false>(p, (int64_t)blockIdx.x - groups, hb, tails);
 }
 
+// the actor alone over the same 16-row groups (vss_actor_forward: an opponent needs actions only)
+template <int NACT>
+__global__ __launch_bounds__(kWaves * 64, 2) void actor_split_kernel(PolicyArgs p) {
+  __shared__ __attribute__((aligned(16))) f32x4 hb[2 * kSplitBuf];
+  __shared__ __attribute__((aligned(16))) float tails[tail_floats(NACT)];
+  split_body<NACT, true>(p, blockIdx.x, hb, tails);
+}
+
 }  // namespace vpol
 
 extern "C" {
@@ -640,6 +648,30 @@ int vss_value_forward_masked(void* stream, int64_t rows, int32_t n_act, const fl
     else hipLaunchKernelGGL((vpol::policy_kernel<6, true>), grid, block, 0, s, a);
   }
   hipLaunchKernelGGL((vpol::policy_kernel<1, false>), grid, block, 0, s, a);
+  return hipGetLastError() == hipSuccess ? VSS_OK : VSS_E_LAUNCH;
+}
+
+int vss_actor_forward(void* stream, int64_t rows, int32_t n_act, const float* obs, const float* actor_packed,
+                      const float* logstd, uint64_t seed, uint64_t counter, float* action_out, float* mean_out) {
+  if (rows < 0 || !obs || !actor_packed || (reinterpret_cast<uintptr_t>(actor_packed) & 15) || !logstd ||
+      !(n_act == 2 || n_act == 6))
+    return VSS_E_ARG;
+  if (rows == 0) return VSS_OK;
+  vpol::PolicyArgs a{rows, obs, actor_packed, nullptr, logstd, nullptr, action_out, nullptr,
+                     nullptr, nullptr, mean_out, seed, counter, nullptr};
+  const int64_t waves = (rows + vpol::kRowsPerWave - 1) / vpol::kRowsPerWave;
+  const int64_t wgs = (waves + vpol::kWaves - 1) / vpol::kWaves;
+  const dim3 block(vpol::kWaves * 64);
+  hipStream_t s = (hipStream_t)stream;
+  if (waves <= vpol::kSplitMaxGroups) {  // small batch: one workgroup per 16-row group, the actor's half only
+    const dim3 grid((unsigned)waves);
+    if (n_act == 2) hipLaunchKernelGGL((vpol::actor_split_kernel<2>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((vpol::actor_split_kernel<6>), grid, block, 0, s, a);
+  } else {
+    const dim3 grid((unsigned)wgs);
+    if (n_act == 2) hipLaunchKernelGGL((vpol::policy_kernel<2, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((vpol::policy_kernel<6, true>), grid, block, 0, s, a);
+  }
   return hipGetLastError() == hipSuccess ? VSS_OK : VSS_E_LAUNCH;
 }
 

@@ -550,13 +550,17 @@ __device__ __forceinline__ void write_obs_record(float* rec, const Bodies& b, co
 // footprints above the cache size and FULL then streams `obs` nontemporally, `terminal_obs` plain.
 // The K-step rollout (K x 175 MB per launch) streams both nontemporally: 36.1 -> 33.3 us per step at
 // K = 16 (obs alone: no gain).
+//
+// A0, REC (the versus step): agents [A0, A0 + A) of the table out of records of REC floats -- the
+// learner's block (A0 = 0) and the yellow team's (A0 = 3) both come from one kRecObs6 record.
 constexpr int kObsUnroll = 4;
-template <int A>
+template <int A, int A0 = 0, int REC = obs_rec<A>()>
 __device__ __forceinline__ void coop_store_obs(float* __restrict__ out, int nv, const float* lds, const uint32_t* tab,
                                                int lane, bool nt = false) {
+  static_assert(A0 + A <= 6 && (A0 == 0 || REC == kRecObs6), "yellow agents read the mirror slots");
   constexpr int Q = 13 * A;  // float4 per field
   constexpr int QD = kWave / Q, QR = kWave % Q;
-  constexpr uint32_t RB = 4u * obs_rec<A>();  // record bytes
+  constexpr uint32_t RB = 4u * REC;  // record bytes
   const int total = nv * Q;
   const uint32_t rb_last = (uint32_t)(nv - 1) * RB;
   int fl = lane / Q, j4 = lane - fl * Q;
@@ -567,7 +571,7 @@ __device__ __forceinline__ void coop_store_obs(float* __restrict__ out, int nv, 
     float4 v[kObsUnroll];
 #pragma unroll
     for (int u = 0; u < kObsUnroll; ++u) {
-      const uint2 t = reinterpret_cast<const uint2*>(tab)[j4];  // LDS copy of kObsTab (stage_obs_table)
+      const uint2 t = reinterpret_cast<const uint2*>(tab)[13 * A0 + j4];  // LDS copy of kObsTab (stage_obs_table)
       const uint32_t r = rb < rb_last ? rb : rb_last;
       v[u].x = *reinterpret_cast<const float*>(L + r + (t.x & 0xffffu));
       v[u].y = *reinterpret_cast<const float*>(L + r + (t.x >> 16));
@@ -1099,6 +1103,187 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
   }
 }
 
+// ---- the versus step: a caller-supplied buffer drives the yellow team ---------------------------------
+// step_kernel<MODE> (SA / CMA / DMA) with the yellow slots 6..11 read from vs.opp_actions instead of
+// the OU process, and the yellow robots' observations after the reset (rows [:, 1] of FULL's obs)
+// written to vs.opp_obs for the opponent's next decision.  Every vss_step_io output keeps the
+// meaning it has in step_kernel<MODE>; the device functions are shared, so the physics, rewards,
+// resets and observation records are the same operation sequences.  The observation records carry
+// the mirror slots (kRecObs6, the LDS of the FULL instantiation); the learner's block and the
+// opponent's stream out of the same record, both nontemporal.
+//
+// SA: blue robots 1-2 (slots 2..5) keep the OU update with the normals ou_noise_split<SA> gives
+// them -- Philox (field, ctr, OU purpose), block 0 words 2-3 (slots 2, 3) and block 1 words 0-1
+// (slots 4, 5), one Box-Muller pair per lane half here -- so the four values equal vss_step(SA)'s
+// bit for bit.  CMA / DMA draw no OU noise.
+template <int MODE>
+__global__ __launch_bounds__(kWave) void step_versus_kernel(StepArgs args, vss_versus_io vs) {
+  static_assert(MODE == VSS_MODE_SA || MODE == VSS_MODE_CMA || MODE == VSS_MODE_DMA, "wrapped modes only");
+  constexpr int A = MODE == VSS_MODE_DMA ? 3 : 1;
+  constexpr int R = MODE == VSS_MODE_DMA ? 3 : 1;
+  constexpr int NL = MODE == VSS_MODE_SA ? 2 : 6;  // learner action floats per field
+  static_assert(2 * kFpw == kWave, "two lanes per field");
+  constexpr int kLds = 32 * kRec > kFpw * kRecObs6 ? 32 * kRec : kFpw * kRecObs6;
+  __shared__ float lds[kLds + kTabWords];
+  uint32_t* tab = reinterpret_cast<uint32_t*>(lds + kLds);
+  stage_obs_table(tab, threadIdx.x);
+
+  const int64_t n = args.n;
+  const int lane = threadIdx.x;
+  const int fl = lane & 31;
+  const bool writer = lane < 32;
+  const uint32_t k0 = (uint32_t)args.p.seed, k1 = (uint32_t)(args.p.seed >> 32);
+  float* rec = lds + fl * kRec;
+  float* orec = lds + lane * kRecObs6;  // observation record (lanes < kFpw)
+
+  const int64_t f0 = (int64_t)blockIdx.x * kFpw;
+  const int nv = (int)(n - f0 < kFpw ? n - f0 : kFpw);
+  BatchIn cur;
+  load_batch<MODE>(args, f0, nv, fl, lane, cur);
+  float2 opp[2];  // the wave's (nv, 6) opponent action rows, with the other inputs
+  prefetch_lrn<6>(vs.opp_actions + f0 * 6, nv, lane, opp);
+  const int64_t f = f0 + fl;
+  const bool valid = fl < nv;
+  const bool owner = valid && writer;
+
+  int64_t progress = cur.progress, reset_prev = cur.reset_prev;
+  const uint32_t ctr = cur.ctr;
+  Bodies b = cur.b;
+
+  // -- actions: the OU buffer (SA: slots 2..5 updated), then the learner's and the opponent's slots --
+  float a[12];
+  stage12(cur.blk, nv, lds, lane);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 12; ++k) a[k] = rec[k];
+  __syncthreads();
+  if constexpr (MODE == VSS_MODE_SA) {
+    const bool up = lane >= 32;
+    uint32_t w[4];
+    philox(k0, k1, (uint32_t)f, ctr, kPurposeOU << 24, up ? 1u : 0u, w);
+    float zc, zs, z[6];
+    box_muller(up ? w[0] : w[2], up ? w[1] : w[3], zc, zs);  // lower: slots 2,3   upper: 4,5
+    exch(zc, z[2], z[4]);
+    exch(zs, z[3], z[5]);
+#pragma unroll
+    for (int k = 2; k < 6; ++k) a[k] = clampf((a[k] - K_OU_THETA * a[k]) + z[k], -1.0f, 1.0f);
+  }
+  stage_lrn<NL>(cur.lrn, nv, lds, lane);
+  stage_lrn<6>(opp, nv, lds + 6, lane);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NL; ++k) a[k] = rec[k];
+#pragma unroll
+  for (int k = 6; k < 12; ++k) a[k] = rec[k];
+  __syncthreads();
+  float ou[12];  // the applied, pre-clamp actions: what ou_buf holds after the call
+#pragma unroll
+  for (int k = 0; k < 12; ++k) ou[k] = a[k];
+
+  const float clip = args.p.clip_actions;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) a[k] = clampf(a[k], -clip, clip);
+  if (reset_prev != 0) progress = 0;
+
+  float pbx = b.bx, pby = b.by, prx[6], pry[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) { prx[i] = b.x[i]; pry[i] = b.y[i]; }
+
+  if (valid) physics_split(b, a);
+
+  progress += 1;
+  float rew[24];
+  const int64_t done = rewards_and_done(args.p, b, pbx, pby, prx, pry, a, progress, rew);
+
+  wait_loads();  // every load retired before the first store (see step_kernel)
+
+  // -- terminal observation: the learner's rows only (no mirror slots needed) -------------------------
+  if (lane < kFpw) write_obs_record<A>(orec, b, a);
+  __syncthreads();
+  coop_store_obs<A, 0, kRecObs6>(args.io.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, true);
+  __syncthreads();
+
+  float dof[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) dof[k] = a[k];
+  if (valid && done) {
+    const ResetDraws rd{k0, k1, (uint32_t)f, ctr, 0u, nullptr, (uint32_t)kMaxRejectRounds};
+    reset_field_split<false>(b, rd);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dof[k] = dof[k] * 0.0f;
+  }
+
+  // -- observations after the reset: the learner's block and the yellow team's, from one record -------
+  if (lane < kFpw) write_obs_record<6>(orec, b, dof);
+  __syncthreads();
+  coop_store_obs<A, 0, kRecObs6>(args.io.obs + f0 * (52 * A), nv, lds, tab, lane, true);
+  coop_store_obs<3, 3, kRecObs6>(vs.opp_obs + f0 * (52 * 3), nv, lds, tab, lane, true);
+  __syncthreads();
+
+  // -- bookkeeping ---------------------------------------------------------------------------------------
+  const uint8_t time_out = (progress >= (int64_t)args.p.max_episode_length - 1) && done != 0;
+  if (owner) {
+    const uint32_t ufl = (uint32_t)fl;
+    store_bodies(args.s.state, n, f0, fl, b);
+    at(args.s.progress_buf + f0, 8u * ufl) = progress;
+    at(args.s.reset_buf + f0, 8u * ufl) = done;
+    at(args.s.rng_counter + f0, 4u * ufl) = ctr + 1u;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+      at(args.io.time_outs + f0 * R, (uint32_t)(ufl * R + k)) = time_out;
+      at(args.io.progress_f + f0 * R, 4u * (ufl * R + k)) = (float)progress;
+    }
+    if constexpr (MODE == VSS_MODE_DMA) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) at(args.io.dones_rep + f0 * 3, 8u * (ufl * 3 + k)) = done;
+    }
+  }
+
+  if (writer) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) rec[k] = dof[k];
+  }
+  __syncthreads();
+  coop_store<12>(args.s.dof_velocity_buf + f0 * 12, nv, lds, lane);
+  __syncthreads();
+  if (writer) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) rec[k] = done ? ou[k] * 0.0f : ou[k];
+  }
+  __syncthreads();
+  coop_store<12>(args.io.ou_buf + f0 * 12, nv, lds, lane);
+  __syncthreads();
+
+  // rewards, as step_kernel<MODE>
+  if constexpr (MODE == VSS_MODE_SA) {
+    if (owner) {
+      at(reinterpret_cast<float4*>(args.io.rew) + f0, 16u * (uint32_t)fl) = make_float4(rew[0], rew[1], rew[2], rew[3]);
+      at(args.io.reward_sum + f0, 4u * (uint32_t)fl) = ((rew[0] + rew[1]) + rew[2]) + rew[3];
+    }
+  } else if constexpr (MODE == VSS_MODE_CMA) {
+    if (owner) {
+      float m[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) m[c] = ((rew[c] + rew[4 + c]) + rew[8 + c]) / 3.0f;
+      at(reinterpret_cast<float4*>(args.io.rew) + f0, 16u * (uint32_t)fl) = make_float4(m[0], m[1], m[2], m[3]);
+      at(args.io.reward_sum + f0, 4u * (uint32_t)fl) = ((m[0] + m[1]) + m[2]) + m[3];
+    }
+  } else {
+    if (writer) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) rec[k] = rew[k];
+    }
+    __syncthreads();
+    coop_store<12>(args.io.rew + f0 * 12, nv, lds, lane);
+    if (owner) {
+#pragma unroll
+      for (int ag = 0; ag < 3; ++ag)
+        at(args.io.reward_sum + f0 * 3, 4u * ((uint32_t)fl * 3 + ag)) =
+            ((rew[4 * ag] + rew[4 * ag + 1]) + rew[4 * ag + 2]) + rew[4 * ag + 3];
+    }
+  }
+}
+
 // ---- K control steps per launch (open-loop action sequences) -----------------------------------------
 // Same per-step semantics as K consecutive step_kernel<FULL> launches, bit for bit (the Philox
 // counter of step k is rng_counter + k), but the field state stays in registers across steps, each
@@ -1366,6 +1551,27 @@ int vss_step(void* stream, int64_t n, int32_t mode, const vss_params* p, const v
 int vss_step_replay(void* stream, int64_t n, int32_t mode, const vss_params* p, const vss_state* st,
                     const vss_step_io* io, const vss_replay_draws* draws) {
   return step_impl<true>(stream, n, mode, p, st, io, draws);
+}
+
+int vss_step_versus(void* stream, int64_t n, int32_t mode, const vss_params* p, const vss_state* st,
+                    const vss_step_io* io, const vss_versus_io* vs) {
+  if (int rc = check_state(n, st)) return rc;
+  if (!p || !io || !vs || mode < VSS_MODE_SA || mode > VSS_MODE_DMA) return VSS_E_ARG;  // FULL takes all 12 itself
+  if (bad(io->actions, 8) || bad(io->ou_buf, 16) || bad(io->obs, 16) || bad(io->terminal_obs, 16) || bad(io->rew, 16) ||
+      bad(io->reward_sum, 4) || bad(io->time_outs, 1) || bad(io->progress_f, 4) || misaligned(io->dones_rep, 8) ||
+      bad(vs->opp_actions, 8) || bad(vs->opp_obs, 16))
+    return VSS_E_ARG;
+  if (mode == VSS_MODE_DMA && !io->dones_rep) return VSS_E_ARG;
+  if (n == 0) return VSS_OK;
+  vss::StepArgs args{n, *p, *st, *io, vss_replay_draws{}, 0u, 0u};
+  const dim3 grid((unsigned)((n + vss::kFpw - 1) / vss::kFpw)), block(vss::kWave);
+  hipStream_t s = (hipStream_t)stream;
+  switch (mode) {
+    case VSS_MODE_SA: hipLaunchKernelGGL((vss::step_versus_kernel<VSS_MODE_SA>), grid, block, 0, s, args, *vs); break;
+    case VSS_MODE_CMA: hipLaunchKernelGGL((vss::step_versus_kernel<VSS_MODE_CMA>), grid, block, 0, s, args, *vs); break;
+    default: hipLaunchKernelGGL((vss::step_versus_kernel<VSS_MODE_DMA>), grid, block, 0, s, args, *vs); break;
+  }
+  return launch_status();
 }
 
 int vss_rollout(void* stream, int64_t n, int32_t k_steps, const vss_params* p, const vss_state* st,

@@ -165,11 +165,8 @@ class VSS:
             raise ValueError(f"{name} must be a contiguous {dtype} tensor of {numel} elements on {self.device}, "
                              f"got {tuple(t.shape)} {t.dtype} on {t.device}")
 
-    def native_step(self, mode: int, actions: torch.Tensor, io: dict) -> None:
-        """One fused step in `mode` (FULL / SA / CMA / DMA) writing into the tensors of `io`.
-
-        Buffers are checked here (size, dtype, device, contiguity); the kernel itself is one
-        launch on the current stream with no host synchronisation."""
+    def _step_io(self, mode: int, actions: torch.Tensor, io: dict):
+        """Check a step's buffers (size, dtype, device, contiguity); (actions, VssStepIO)."""
         n = self.num_fields
         if mode not in (N.MODE_FULL, N.MODE_SA, N.MODE_CMA, N.MODE_DMA):
             raise ValueError(f"unknown mode {mode}")
@@ -193,10 +190,35 @@ class VSS:
         cio = N.VssStepIO(actions.data_ptr(), N.ptr(io.get("ou_buf")), N.ptr(io["obs"]),
                           N.ptr(io["terminal_obs"]), N.ptr(io["rew"]), N.ptr(io.get("reward_sum")),
                           N.ptr(io.get("dones_rep")), N.ptr(io["time_outs"]), N.ptr(io["progress_f"]))
+        return actions, cio
+
+    def native_step(self, mode: int, actions: torch.Tensor, io: dict) -> None:
+        """One fused step in `mode` (FULL / SA / CMA / DMA) writing into the tensors of `io`.
+
+        Buffers are checked here (size, dtype, device, contiguity); the kernel itself is one
+        launch on the current stream with no host synchronisation."""
+        actions, cio = self._step_io(mode, actions, io)
         prm, st = self._c_params(), self._c_state()
-        rc = N.load().vss_step(N.stream_of(self.device), n, mode, N.ctypes.byref(prm), N.ctypes.byref(st),
-                               N.ctypes.byref(cio))
+        rc = N.load().vss_step(N.stream_of(self.device), self.num_fields, mode, N.ctypes.byref(prm),
+                               N.ctypes.byref(st), N.ctypes.byref(cio))
         N.check(rc, "vss_step")
+
+    def native_step_versus(self, mode: int, actions: torch.Tensor, io: dict, opp_actions: torch.Tensor,
+                           opp_obs: torch.Tensor) -> None:
+        """native_step in mode SA / CMA / DMA with the yellow team driven by `opp_actions` (N,3,2)
+        instead of OU noise (vss_step_versus); the yellow robots' observations after the step's
+        reset are written to `opp_obs` (N,3,52).  Same buffer checks, one launch, no host sync."""
+        if mode == N.MODE_FULL:
+            raise ValueError("the versus step is for SA / CMA / DMA; FULL takes all twelve actions itself")
+        actions, cio = self._step_io(mode, actions, io)
+        n = self.num_fields
+        self._check_buffer("opp_actions", opp_actions, n * 6, torch.float32)
+        self._check_buffer("opp_obs", opp_obs, n * 3 * 52, torch.float32)
+        vio = N.VssVersusIO(opp_actions.data_ptr(), opp_obs.data_ptr())
+        prm, st = self._c_params(), self._c_state()
+        rc = N.load().vss_step_versus(N.stream_of(self.device), n, mode, N.ctypes.byref(prm), N.ctypes.byref(st),
+                                      N.ctypes.byref(cio), N.ctypes.byref(vio))
+        N.check(rc, "vss_step_versus")
 
     def step(self, actions: torch.Tensor):
         """Ext VecTask.step + VSS.pre/post_physics_step for every field (one HIP launch)."""

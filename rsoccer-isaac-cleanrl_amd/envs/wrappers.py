@@ -38,7 +38,12 @@ def _local_device() -> str:
 
 
 def make_env(args):
-    """(unwrapped VSS, wrapped env) for args.env_id in {sa, cma, dma} (envs/wrappers.py:21-48)."""
+    """(unwrapped VSS, wrapped env) for args.env_id in {sa, cma, dma} (envs/wrappers.py:21-48).
+
+    args.opponent ('ou' when absent) is only validated here: the returned wrapper drives the yellow
+    team with OU noise until its set_opponent(team) is called.  A policy opponent needs the Agent,
+    which exists only after the env, so the train loop (or any other caller) builds the team --
+    vss_amd.opponent.SnapshotOpponent -- and calls set_opponent itself."""
     assert args.cuda
     cfg = default_cfg(args.num_envs)
     if args.env_id == "dma":
@@ -51,6 +56,10 @@ def make_env(args):
                headless=not getattr(args, "capture_video", False),
                virtual_screen_capture=getattr(args, "capture_video", False), force_render=False)
     wrappers = {"sa": SingleAgent, "cma": CMA, "dma": DMA}
+    opponent = getattr(args, "opponent", "ou")
+    if opponent != "ou" and not (opponent == "self" or os.path.exists(opponent)):
+        raise ValueError(f"--opponent must be ou, self or a checkpoint path, got {opponent!r}")
+    # the opponent itself (a snapshot of the Agent) is set by the train loop: set_opponent()
     return envs, wrappers[args.env_id](envs)
 
 
@@ -117,13 +126,38 @@ class _FusedWrapper(Wrapper):
             self._progress = torch.zeros(rows, device=dev)
             self._dones = torch.zeros(rows, dtype=torch.long, device=dev)
         env.compute_observations(self._obs, n_agents=3 if self.ROWS_PER_FIELD == 3 else 1)
+        self._opponent = None  # yellow team policy (set_opponent); None: the kernel's OU process
+        self._opp_obs = self._opp_act = None
 
     def _first_obs(self):
         self.env.compute_observations(self._obs, n_agents=3 if self.ROWS_PER_FIELD == 3 else 1)
         return {"obs": self._obs}
 
+    def _first_opp_obs(self):
+        """The yellow robots' observations of the current state (rows [:, 1] of the FULL layout);
+        once per reset / set_opponent -- every versus step then writes them itself."""
+        env = self.env
+        full = torch.empty((env.num_fields, 2, 3, env.num_obs), device=env.device)
+        env.compute_observations(full, n_agents=6)
+        self._opp_obs.copy_(full[:, 1])
+
+    def set_opponent(self, team=None):
+        """Drive the yellow team with `team` -- play.py's protocol, team(act (N,3,2) written in place,
+        obs (N,3,52)) -- inside the fused step (vss_step_versus) instead of OU noise; None (the
+        default) restores the OU opponent and step() is the plain path again."""
+        self._opponent = team
+        if team is None:
+            return
+        if self._opp_obs is None:
+            n, dev = self.env.num_fields, self.env.device
+            self._opp_obs = torch.zeros((n, 3, self.env.num_obs), device=dev)
+            self._opp_act = torch.zeros((n, 3, 2), device=dev)
+        self._first_opp_obs()
+
     def reset(self, **kwargs):
         self.env.reset(**kwargs)
+        if self._opponent is not None:
+            self._first_opp_obs()
         return self._first_obs()
 
     def _rews_view(self):
@@ -131,12 +165,17 @@ class _FusedWrapper(Wrapper):
 
     def step(self, action):
         env = self.env
-        env.native_step(self.MODE, action, dict(
-            ou_buf=self.action_buf, obs=self._obs, terminal_obs=self._terminal_obs, rew=self._rews,
-            reward_sum=self._reward, dones_rep=self._dones, time_outs=self._time_outs,
-            progress_f=self._progress))
+        io = dict(ou_buf=self.action_buf, obs=self._obs, terminal_obs=self._terminal_obs, rew=self._rews,
+                  reward_sum=self._reward, dones_rep=self._dones, time_outs=self._time_outs,
+                  progress_f=self._progress)
         infos = {"rews": self._rews_view(), "terminal_observation": self._terminal_obs,
                  "time_outs": self._time_outs, "progress_buffer": self._progress}
+        if self._opponent is None:
+            env.native_step(self.MODE, action, io)
+        else:
+            self._opponent(self._opp_act, self._opp_obs)
+            env.native_step_versus(self.MODE, action, io, self._opp_act, self._opp_obs)
+            infos["opponent_obs"] = self._opp_obs
         dones = env.reset_buf if self._dones is None else self._dones
         return {"obs": self._obs}, self._reward, dones, infos
 

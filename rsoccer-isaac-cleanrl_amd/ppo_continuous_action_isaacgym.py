@@ -20,7 +20,9 @@ the loop -- and the machinery under it lives in vss_amd/:
   --norm-adv normalises over all ranks' rows; approx_kl is averaged over ranks when it drives a decision;
 * no per-element host-synchronising logging loop (ppo…:273-279): episode statistics are
   reduced on the device and read once per update;
-* logging is optional (TensorBoard if installed, else a CSV of the same scalars; no W&B).
+* logging is optional (TensorBoard if installed, else a CSV of the same scalars; no W&B);
+* `--opponent self|PATH` (a build addition): the yellow team is a policy -- a snapshot of the learner, refreshed
+  every `--opponent-update-every` updates, or a checkpoint -- instead of OU noise (vss_amd/opponent.py).
 """
 from __future__ import annotations
 
@@ -115,6 +117,13 @@ def parse_args(argv=None):
                         "throwaway env and agent (16,384 envs x 8 steps), so the runtime loads the code objects of "
                         "the kernels the loop uses outside the clock (warmup_kernels; its time is kept in "
                         "args.kernel_warmup_s); the training itself is unchanged")
+    p.add_argument("--opponent", type=str, default="ou",
+                   help="the yellow team: 'ou' (Ornstein-Uhlenbeck noise, the reference's wrappers), 'self' (a frozen "
+                        "snapshot of the learner's actor, vss_amd.opponent.SnapshotOpponent, inside the fused step) or "
+                        "the path of an agent checkpoint in the reference's format (a fixed opponent)")
+    p.add_argument("--opponent-update-every", type=int, default=1,
+                   help="--opponent self: copy the learner's weights into the snapshot after every K-th update "
+                        "(0: keep the initial weights)")
     args = p.parse_args(argv)
     args.batch_size = int(args.num_envs * args.num_steps)
     args.minibatch_size = int(args.batch_size // args.num_minibatches)
@@ -355,6 +364,7 @@ def train(args, on_update=None):
 
     from envs.wrappers import RecordEpisodeStatisticsTorch, make_env
     unwrapped_env, envs = make_env(args)
+    fused_env = envs  # the SA / CMA / DMA wrapper itself (set_opponent), under the wrappers added below
     video = None
     if args.capture_video and rank == 0:  # ppo…:213-221 (GIF clips of field 0, envs/render.py)
         from envs.render import RecordVideo
@@ -373,6 +383,24 @@ def train(args, on_update=None):
     if args.fused_policy and device.type == "cuda" and args.amp == "none":
         from vss_amd.policy import FusedPolicy, TerminalValues
         fused = FusedPolicy(agent, seed=seed * 7919 + 17)
+    # --opponent self | PATH: the yellow team is a frozen copy of this Agent's actor (or a checkpoint's) inside
+    # the fused step, with a Philox stream of its own; 'ou' leaves the wrapper on the kernel's OU process.
+    # The weights are the same on every rank, so sync() is a local copy (no collective).
+    opponent = None
+    opponent_mode = getattr(args, "opponent", "ou")
+    if opponent_mode != "ou":
+        from vss_amd.opponent import KIND_OF_ENV, SnapshotOpponent
+        opponent = SnapshotOpponent(agent, KIND_OF_ENV[args.env_id], seed=seed * 7919 + 104729)
+        if opponent_mode != "self":
+            opponent.load(opponent_mode)
+        fused_env.set_opponent(opponent)
+        if getattr(args, "kernel_warmup", False):
+            # outside the clock, like warmup_kernels below: the opponent's forward at this run's own row count
+            # (under 16,384 opponent rows it is the actor-only fused kernel, which the 16,384-env warm-up run
+            # does not reach); the Philox counter is put back, so the training's draws do not change
+            counter = opponent.policy.counter
+            opponent(torch.zeros_like(fused_env._opp_act), fused_env._opp_obs)
+            opponent.policy.counter = counter
     # torch's Adam (ppo…:166) -- on the GPU FlatAdam: the same update rule over the flat parameter and
     # gradient buffers, with the gradient clip, in one launch per minibatch (vss_adam_step_clipped)
     if device.type == "cuda":
@@ -475,10 +503,13 @@ def train(args, on_update=None):
         wall = time.time() - start_time
         sps = int(global_step / wall)
         rec = {"update": update, "global_step": global_step, "sps": sps, "wall_s": wall, "rollout_s": t_roll,
-               "update_s": t_upd,
+               "update_s": t_upd, "opponent_version": opponent.version if opponent is not None else -1,
                "episodes": float(ep_cnt.sum()), "mean_return": float(ep_ret.sum() / ep_cnt.sum().clamp(min=1)),
                **{k: float(v) for k, v in stats.items()}}
         history.append(rec)
+        every = getattr(args, "opponent_update_every", 1)
+        if opponent is not None and opponent_mode == "self" and every > 0 and update % every == 0:
+            opponent.sync(agent, version=update)
         for k, name in (("v_loss", "value_loss"), ("pg_loss", "policy_loss"), ("entropy", "entropy"),
                         ("old_approx_kl", "old_approx_kl"), ("approx_kl", "approx_kl"), ("clipfrac", "clipfrac")):
             writer.add_scalar(f"losses/{name}", rec[k], global_step)

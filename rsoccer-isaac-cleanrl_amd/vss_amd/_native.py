@@ -49,7 +49,8 @@ MODE_FULL, MODE_SA, MODE_CMA, MODE_DMA = 0, 1, 2, 3
 STATE_CHANNELS = 58
 CH_BALL_X, CH_BALL_Y, CH_BALL_VX, CH_BALL_VY = 0, 1, 2, 3
 CH_RX, CH_RY, CH_RQX, CH_RQY, CH_RQZ, CH_RQW, CH_RVX, CH_RVY, CH_RW = 4, 10, 16, 22, 28, 34, 40, 46, 52
-EXPORTED = ("vss_abi_version", "vss_source_hash", "vss_error_string", "vss_step", "vss_step_replay", "vss_rollout", "vss_reset_dones",
+EXPORTED = ("vss_abi_version", "vss_source_hash", "vss_error_string", "vss_step", "vss_step_replay", "vss_step_versus",
+            "vss_actor_forward", "vss_rollout", "vss_reset_dones",
             "vss_reset_dones_replay",
             "vss_compute_observations", "vss_mlp_packed_size", "vss_mlp_pack", "vss_policy_forward",
             "vss_value_forward_masked", "vss_policy_sample", "vss_episode_stats", "vss_tanh_grad_chunks", "vss_tanh_grad_bias",
@@ -86,6 +87,11 @@ class VssStepIO(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in
                 ("actions", "ou_buf", "obs", "terminal_obs", "rew", "reward_sum", "dones_rep",
                  "time_outs", "progress_f")]
+
+
+class VssVersusIO(ctypes.Structure):
+    """The yellow team's side of vss_step_versus (include/vss.h vss_versus_io)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("opp_actions", "opp_obs")]
 
 
 class VssRolloutIO(ctypes.Structure):
@@ -149,6 +155,8 @@ def load() -> ctypes.CDLL:
     L.vss_step.restype = ctypes.c_int
     L.vss_step_replay.argtypes = [P, i64, i32, P, P, P, P]
     L.vss_step_replay.restype = ctypes.c_int
+    L.vss_step_versus.argtypes = [P, i64, i32, P, P, P, P]
+    L.vss_step_versus.restype = ctypes.c_int
     L.vss_reset_dones_replay.argtypes = [P, i64, P, P, P]
     L.vss_reset_dones_replay.restype = ctypes.c_int
     L.vss_rollout.argtypes = [P, i64, i32, P, P, P]
@@ -165,6 +173,8 @@ def load() -> ctypes.CDLL:
     L.vss_policy_forward.restype = ctypes.c_int
     L.vss_value_forward_masked.argtypes = [P, i64, i32, P, P, P, P, ctypes.c_uint64, ctypes.c_uint64] + [P] * 7
     L.vss_value_forward_masked.restype = ctypes.c_int
+    L.vss_actor_forward.argtypes = [P, i64, i32, P, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P]
+    L.vss_actor_forward.restype = ctypes.c_int
     L.vss_policy_sample.argtypes = [P, i64, i32, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P, P, P]
     L.vss_policy_sample.restype = ctypes.c_int
     L.vss_episode_stats.argtypes = [P, i64] + [P] * 7

@@ -34,8 +34,11 @@ ROLLOUT_POLICY = os.environ.get("VSS_ROLLOUT_POLICY", "chain")
 
 
 class FusedPolicy:
-    def __init__(self, agent, seed: int = 0):
+    def __init__(self, agent, seed: int = 0, actor_only: bool = False):
+        """actor_only: `agent` has no critic (an opponent's frozen actor): act() and actor_mean() work,
+        every method that needs the critic raises ValueError."""
         self.agent = agent
+        self.actor_only = bool(actor_only)
         self.device = next(agent.parameters()).device
         N.require_device(self.device)
         self.n_act = int(agent.actor_logstd.shape[-1])
@@ -43,7 +46,7 @@ class FusedPolicy:
             raise ValueError("fused policy supports 2 (SA/DMA) or 6 (CMA) actions")
         lib = N.load()
         self._actor = torch.empty(lib.vss_mlp_packed_size(self.n_act), device=self.device)
-        self._critic = torch.empty(lib.vss_mlp_packed_size(1), device=self.device)
+        self._critic = None if self.actor_only else torch.empty(lib.vss_mlp_packed_size(1), device=self.device)
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.counter = 0
         self._keep = {}
@@ -71,10 +74,12 @@ class FusedPolicy:
         packed weights and the GEMM chain's bf16 weight planes (one vss_weight_planes_bf16x6 launch for
         both MLPs' hidden layers, instead of a split launch per layer and rollout step)."""
         self._pack(self.agent.actor_mean, self.n_act, self._actor)
-        self._pack(self.agent.critic, 1, self._critic)
+        nets = (self.agent.actor_mean,) if self.actor_only else (self.agent.actor_mean, self.agent.critic)
+        if not self.actor_only:
+            self._pack(self.agent.critic, 1, self._critic)
         self._planes = {}
         if ROLLOUT_POLICY == "chain":
-            jobs = [(id(seq), i, m.weight.detach()) for seq in (self.agent.actor_mean, self.agent.critic)
+            jobs = [(id(seq), i, m.weight.detach()) for seq in nets
                     for i, m in enumerate(self._linears(seq)[1:-1], 1)
                     if m.weight.dtype == torch.float32 and m.weight.is_contiguous()
                     and x6_ok(256, m.in_features, m.out_features)]
@@ -101,6 +106,7 @@ class FusedPolicy:
         """critic(obs) through the GEMM chain for ANY row count, padded to whole 256-row tiles so every
         row takes the same kernels as in a chain-sized batch: a row's value does not depend on the
         batch it is evaluated in (the masked terminal pass of the rollout relies on it)."""
+        self._need_critic()
         obs = obs.reshape(-1, 52).to(self.device, torch.float32)
         rows = obs.shape[0]
         pad = -rows % 256
@@ -108,7 +114,12 @@ class FusedPolicy:
             obs = torch.cat([obs, obs.new_zeros((pad, 52))])
         return self._chain(self.agent.critic, obs.contiguous())[:rows]
 
+    def _need_critic(self):
+        if self.actor_only:
+            raise ValueError("an actor-only FusedPolicy has no critic: use act() / actor_mean()")
+
     def _run(self, obs, actor: bool, action=None, out=None, want_mean=False):
+        self._need_critic()
         obs = obs.reshape(-1, 52)
         if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device:
             obs = obs.to(self.device, torch.float32).contiguous()
@@ -189,6 +200,7 @@ class FusedPolicy:
     def get_value_masked(self, obs, mask: torch.Tensor, out: torch.Tensor):
         """critic(obs) written into `out` (rows, 1) only for rows with mask != 0 (int64 mask,
         e.g. the env's dones); other rows of `out` are left untouched."""
+        self._need_critic()
         obs = obs.reshape(-1, 52).to(self.device, torch.float32).contiguous()
         rows = obs.shape[0]
         mask = mask.to(self.device, torch.long).contiguous()
@@ -203,7 +215,38 @@ class FusedPolicy:
 
     @torch.no_grad()
     def actor_mean(self, obs):
+        if self.actor_only:
+            return self.act(obs, want_mean=True)[1]
         return self._run(obs, True, want_mean=True)[4]
+
+    @torch.no_grad()
+    def act(self, obs, out=None, want_mean=False):
+        """The sampled action alone (rows, n_act), no critic pass: what an opponent needs.  Same Philox
+        stream and sampling formula as get_action_and_value (equal seed, counter and row: equal
+        action).  At chain sizes the actor's GEMM chain + vss_policy_sample, else the actor-only fused
+        kernel (vss_actor_forward).  out: a contiguous fp32 buffer of rows x n_act written in place.
+        want_mean: return (action, mean)."""
+        obs = obs.reshape(-1, 52)
+        if obs.dtype != torch.float32 or not obs.is_contiguous() or obs.device != self.device:
+            obs = obs.to(self.device, torch.float32).contiguous()
+        rows, dev = obs.shape[0], self.device
+        if out is None:
+            out = torch.empty((rows, self.n_act), device=dev)
+        elif out.numel() != rows * self.n_act or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError("out must be a contiguous fp32 buffer of rows x n_act on the policy's device")
+        logstd = self.agent.actor_logstd.detach()
+        self.counter += 1
+        if self.chain_active(rows):
+            mean = self._chain(self.agent.actor_mean, obs).contiguous()
+            N.check(N.load().vss_policy_sample(N.stream_of(dev), rows, self.n_act, mean.data_ptr(), logstd.data_ptr(),
+                                               self.seed, self.counter, None, out.data_ptr(), None, None),
+                    "vss_policy_sample")
+        else:
+            mean = torch.empty((rows, self.n_act), device=dev) if want_mean else None
+            N.check(N.load().vss_actor_forward(N.stream_of(dev), rows, self.n_act, obs.data_ptr(), self._actor.data_ptr(),
+                                               logstd.data_ptr(), self.seed, self.counter, out.data_ptr(), N.ptr(mean)),
+                    "vss_actor_forward")
+        return (out, mean) if want_mean else out
 
 
 class TerminalValues:
