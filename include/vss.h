@@ -294,6 +294,42 @@ int vss_policy_sample(void* stream, int64_t rows, int32_t n_act, const float* me
                       uint64_t counter, const float* action_in, float* action_out, float* logprob_out,
                       float* entropy_out);
 
+/*
+ * Several actors in one launch (an opponent pool: vss_amd/opponent.py OpponentPool).  The rows are cut
+ * into `count` groups of `group_rows` rows (the last may be shorter); group g is evaluated with
+ * actor_packed[g] and logstd[g].  A host struct: the pointers travel to the kernel as kernel arguments.
+ */
+#define VSS_MAX_ACTOR_GROUPS 16
+typedef struct vss_actor_groups {
+  int32_t count;            /* 1..VSS_MAX_ACTOR_GROUPS */
+  int64_t group_rows;       /* rows per group: > 0, a multiple of 64; group g owns rows
+                               [g*group_rows, min(rows, (g+1)*group_rows));
+                               (count-1)*group_rows < rows <= count*group_rows */
+  const float* actor_packed[VSS_MAX_ACTOR_GROUPS];  /* vss_mlp_pack output, 16-B aligned; entries >= count unused */
+  const float* logstd[VSS_MAX_ACTOR_GROUPS];        /* (n_act,) each */
+} vss_actor_groups;
+
+/*
+ * vss_actor_forward with per-group weights: row r uses actor_packed[r / group_rows] and
+ * logstd[r / group_rows]; the Philox row is the global row r.  The rows of group g in action_out /
+ * mean_out are bit-identical to vss_actor_forward(rows, ..., actor_packed[g], logstd[g], seed, counter, ...)
+ * over the whole batch (count == 1: the whole output).  The kernel is chosen by the total row count,
+ * as in vss_actor_forward.  VSS_E_ARG: a null group / obs / used weight or log-std pointer, a misaligned
+ * actor_packed, count outside 1..16, group_rows not a positive multiple of 64, rows outside
+ * ((count-1)*group_rows, count*group_rows] (rows == 0 is VSS_OK, no launch), n_act not in {2, 6}.
+ */
+int vss_actor_forward_grouped(void* stream, int64_t rows, int32_t n_act, const float* obs, const vss_actor_groups* g,
+                              uint64_t seed, uint64_t counter, float* action_out, float* mean_out);
+
+/*
+ * vss_policy_sample's action draw with logstd[row / group_rows] and the global row as the Philox row
+ * (means from per-group GEMM chains): the rows of group g equal vss_policy_sample(rows, ..., logstd[g],
+ * ..., action_out, NULL, NULL) over the whole batch.  actor_packed is not read and may be NULL.
+ * Argument checks as vss_actor_forward_grouped (mean in place of obs).
+ */
+int vss_policy_sample_grouped(void* stream, int64_t rows, int32_t n_act, const float* mean, const vss_actor_groups* g,
+                              uint64_t seed, uint64_t counter, float* action_out);
+
 /* ---------------------------------------------------------------------------------------------
  * PPO-update helper: the backward of a hidden layer's tanh
  * (ppo_continuous_action_isaacgym.py:104-111, autograd of nn.Tanh + nn.Linear's bias) in one pass:
@@ -572,6 +608,20 @@ int vss_sum_parts(void* stream, int32_t count, const float* const* src, float* c
  * ------------------------------------------------------------------------------------------- */
 int vss_episode_stats(void* stream, int64_t rows, const float* rews, const int64_t* dones, float* ep_returns,
                       int32_t* ep_lengths, float* returned_returns, int32_t* returned_lengths, float* return_sum);
+
+/*
+ * Match results per opponent group, after a versus step: for every field f whose learner row
+ * r = f * rows_per_field has dones[r] != 0, with q = f / group_fields,
+ *   tally[q][0] += 1 (episodes); tally[q][1] += 1 if rew[r][0] > 0 (the learner scored);
+ *   tally[q][2] += 1 if rew[r][0] < 0 (the learner conceded); tally[q][3] += (int64) progress_f[r] (steps).
+ * The goal term's sign tells who scored only for w_goal > 0 (the caller's check).  Integer adds only:
+ * exact, independent of order.  Accumulates -- the caller zeroes tally (count, 4) int64.  rew
+ * (n_fields * rows_per_field, 4) fp32, 16-B aligned; dones int64 and progress_f fp32 over the same rows.
+ * VSS_E_ARG: rows_per_field not 1 or 3, group_fields <= 0, count outside 1..16,
+ * count * group_fields < n_fields, a null or misaligned pointer.  n_fields == 0: VSS_OK, no launch.
+ */
+int vss_match_tally(void* stream, int64_t n_fields, int32_t rows_per_field, int64_t group_fields, int32_t count,
+                    const float* rew, const int64_t* dones, const float* progress_f, int64_t* tally);
 
 #ifdef __cplusplus
 }

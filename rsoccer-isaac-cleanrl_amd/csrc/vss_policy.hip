@@ -585,6 +585,134 @@ __global__ __launch_bounds__(kWaves * 64, 2) void actor_split_kernel(PolicyArgs 
   split_body<NACT, true>(p, blockIdx.x, hb, tails);
 }
 
+// ---- several actors in one launch (vss_actor_forward_grouped: an opponent pool) -------------------------
+// Group g owns rows [g group_rows, (g + 1) group_rows); group_rows is a multiple of 64, so neither a
+// 16-row nor a 64-row workgroup straddles two groups and the choice of weights is uniform over the
+// workgroup.  The table travels as kernel arguments (indexed with a scalar, read with scalar loads).
+struct GroupedArgs {
+  PolicyArgs p;  // actor / logstd are filled in per workgroup
+  int64_t group_rows;
+  int32_t count;
+  const float* actor[VSS_MAX_ACTOR_GROUPS];
+  const float* logstd[VSS_MAX_ACTOR_GROUPS];
+};
+
+// Which row block a workgroup takes.  0: block b takes row block b.  1: the workgroups of group g sit on
+// blockIdx = g (mod 8) -- blocks b and b + 8 were observed to share an XCD, so one XCD's L2 then holds
+// one (count <= 8) or two weight streams instead of all of them.  A speed matter only: every row block is
+// taken by exactly one workgroup either way, and a row's arithmetic does not depend on the workgroup's
+// index.  Residue r = b % 8 serves group r % count (count <= 8: group g has the residues g, g + count, ...)
+// or, for count > 8, groups r and r + 8 in turn; workgroups past a group's last row block exit at once; one
+// group alone keeps block b on row block b.
+// Measured, 8 groups (tools/league_bench.py, profiles/league_bench.json): mapping 1 is kept --
+// 4,096 rows (split kernel, weights read straight from L2) 60 us against 103 us with mapping 0 and 59 us for
+// one weight set; 12,288 rows (staged weights) 150 against 155-157 and 150 us.
+#ifndef VSS_GROUPED_XCD_MAP
+#define VSS_GROUPED_XCD_MAP 1
+#endif
+#if VSS_GROUPED_XCD_MAP
+constexpr int kXcds = 8;
+#endif
+
+__host__ __device__ inline int64_t grouped_blocks_of(int64_t rows, int64_t group_rows, int g, int rpb) {
+  const int64_t first = (int64_t)g * group_rows;
+  const int64_t n = rows - first < group_rows ? rows - first : group_rows;
+  return n <= 0 ? 0 : (n + rpb - 1) / rpb;
+}
+
+// the grid of a grouped launch with RPB rows per workgroup
+inline int64_t grouped_grid(int64_t rows, int64_t group_rows, int count, int rpb) {
+#if VSS_GROUPED_XCD_MAP
+  int64_t per_residue = 0;
+  for (int g = 0; g < count; ++g) {
+    const int64_t nb = grouped_blocks_of(rows, group_rows, g, rpb);
+    const int nres = count <= kXcds ? (kXcds - g + count - 1) / count : 1;
+    const int64_t need = count <= kXcds ? (nb + nres - 1) / nres : 2 * nb;
+    if (need > per_residue) per_residue = need;
+  }
+  return per_residue * kXcds;
+#else
+  (void)group_rows; (void)count;
+  return (rows + rpb - 1) / rpb;
+#endif
+}
+
+// false: this workgroup has no row block (uniform over the workgroup)
+template <int RPB>
+__device__ __forceinline__ bool grouped_block(const GroupedArgs& a, int64_t& blk, int& g) {
+#if VSS_GROUPED_XCD_MAP
+  const int r = (int)(blockIdx.x % kXcds);
+  const int64_t j = blockIdx.x / kXcds;
+  int64_t local;
+  if (a.count == 1) {
+    g = 0;
+    local = blockIdx.x;
+  } else if (a.count <= kXcds) {
+    g = r % a.count;
+    const int nres = (kXcds - g + a.count - 1) / a.count;
+    local = j * nres + r / a.count;
+  } else {
+    g = r + kXcds * (int)(j & 1);
+    local = j >> 1;
+    if (g >= a.count) return false;
+  }
+  if (local >= grouped_blocks_of(a.p.rows, a.group_rows, g, RPB)) return false;
+  blk = (int64_t)g * (a.group_rows / RPB) + local;
+#else
+  blk = blockIdx.x;
+  g = (int)(blk * RPB / a.group_rows);
+#endif
+  return true;
+}
+
+template <int NACT>
+__global__ __launch_bounds__(kWaves * 64, 2) void actor_split_grouped_kernel(GroupedArgs a) {
+  __shared__ __attribute__((aligned(16))) f32x4 hb[2 * kSplitBuf];
+  __shared__ __attribute__((aligned(16))) float tails[tail_floats(NACT)];
+  int64_t blk;
+  int g;
+  if (!grouped_block<kRowsPerWave>(a, blk, g)) return;
+  PolicyArgs p = a.p;
+  p.actor = a.actor[g];
+  p.logstd = a.logstd[g];
+  split_body<NACT, true>(p, blk, hb, tails);
+}
+
+template <int NACT>
+__global__ __launch_bounds__(kWaves * 64) void policy_grouped_kernel(GroupedArgs a) {
+  __shared__ __attribute__((aligned(16))) f32x4 lds[2 * kChunkF4];
+  __shared__ __attribute__((aligned(16))) float tails[tail_floats(NACT)];
+  int64_t blk;
+  int g;
+  if (!grouped_block<kWaves * kRowsPerWave>(a, blk, g)) return;
+  PolicyArgs p = a.p;
+  p.actor = a.actor[g];
+  p.logstd = a.logstd[g];
+  policy_body<NACT, true>(p, blk, lds, tails);
+}
+
+// sample_kernel's action draw with the log-std of the row's group; a wave's 64 rows start at a multiple
+// of 64, so the group is uniform over the wave
+struct SampleGroups {
+  int64_t group_rows;
+  const float* logstd[VSS_MAX_ACTOR_GROUPS];
+};
+
+template <int NACT>
+__global__ __launch_bounds__(256) void sample_grouped_kernel(int64_t rows, const float* __restrict__ mean, SampleGroups t,
+                                                             uint64_t seed, uint64_t counter, float* action_out) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t base = (int64_t)blockIdx.x * 256 + wave * 64;
+  if (base >= rows) return;
+  const float* logstd = t.logstd[base / t.group_rows];
+  const int64_t row = base + (threadIdx.x & 63);
+  if (row >= rows) return;
+  float m[NACT];
+#pragma unroll
+  for (int a = 0; a < NACT; ++a) m[a] = mean[row * NACT + a];
+  actor_tail<NACT>(m, row, logstd, seed, counter, nullptr, action_out, nullptr, nullptr, nullptr);
+}
+
 }  // namespace vpol
 
 extern "C" {
@@ -688,6 +816,69 @@ int vss_policy_sample(void* stream, int64_t rows, int32_t n_act, const float* me
   else
     hipLaunchKernelGGL(vpol::sample_kernel<6>, grid, block, 0, s, rows, mean, logstd, seed, counter, action_in,
                        action_out, logprob_out, entropy_out);
+  return hipGetLastError() == hipSuccess ? VSS_OK : VSS_E_LAUNCH;
+}
+
+// the group table's own checks, before the row count is looked at (need_actor: the packed weights are read)
+static int check_groups(int64_t rows, int32_t n_act, const vss_actor_groups* g, bool need_actor) {
+  if (rows < 0 || !g || !(n_act == 2 || n_act == 6)) return VSS_E_ARG;
+  if (g->count < 1 || g->count > VSS_MAX_ACTOR_GROUPS) return VSS_E_ARG;
+  if (g->group_rows <= 0 || g->group_rows % 64 != 0 || g->group_rows > (int64_t(1) << 40)) return VSS_E_ARG;
+  for (int i = 0; i < g->count; ++i) {
+    if (!g->logstd[i] || (reinterpret_cast<uintptr_t>(g->logstd[i]) & 3)) return VSS_E_ARG;
+    if (need_actor && (!g->actor_packed[i] || (reinterpret_cast<uintptr_t>(g->actor_packed[i]) & 15))) return VSS_E_ARG;
+  }
+  return VSS_OK;
+}
+
+// rows > 0 must reach the last group and not pass it
+static bool rows_fit(int64_t rows, const vss_actor_groups* g) {
+  return rows > (g->count - 1) * g->group_rows && rows <= g->count * g->group_rows;
+}
+
+int vss_actor_forward_grouped(void* stream, int64_t rows, int32_t n_act, const float* obs, const vss_actor_groups* g,
+                              uint64_t seed, uint64_t counter, float* action_out, float* mean_out) {
+  if (int rc = check_groups(rows, n_act, g, true)) return rc;
+  if (!obs) return VSS_E_ARG;
+  if (rows == 0) return VSS_OK;
+  if (!rows_fit(rows, g)) return VSS_E_ARG;
+  vpol::GroupedArgs a;
+  a.p = vpol::PolicyArgs{rows, obs, nullptr, nullptr, nullptr, nullptr, action_out, nullptr,
+                         nullptr, nullptr, mean_out, seed, counter, nullptr};
+  a.group_rows = g->group_rows;
+  a.count = g->count;
+  for (int i = 0; i < VSS_MAX_ACTOR_GROUPS; ++i) {  // entries past count: never indexed
+    a.actor[i] = i < g->count ? g->actor_packed[i] : nullptr;
+    a.logstd[i] = i < g->count ? g->logstd[i] : nullptr;
+  }
+  const int64_t waves = (rows + vpol::kRowsPerWave - 1) / vpol::kRowsPerWave;
+  const dim3 block(vpol::kWaves * 64);
+  hipStream_t s = (hipStream_t)stream;
+  if (waves <= vpol::kSplitMaxGroups) {  // the same choice of kernel as vss_actor_forward, by the total row count
+    const dim3 grid((unsigned)vpol::grouped_grid(rows, g->group_rows, g->count, vpol::kRowsPerWave));
+    if (n_act == 2) hipLaunchKernelGGL((vpol::actor_split_grouped_kernel<2>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((vpol::actor_split_grouped_kernel<6>), grid, block, 0, s, a);
+  } else {
+    const dim3 grid((unsigned)vpol::grouped_grid(rows, g->group_rows, g->count, vpol::kWaves * vpol::kRowsPerWave));
+    if (n_act == 2) hipLaunchKernelGGL((vpol::policy_grouped_kernel<2>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((vpol::policy_grouped_kernel<6>), grid, block, 0, s, a);
+  }
+  return hipGetLastError() == hipSuccess ? VSS_OK : VSS_E_LAUNCH;
+}
+
+int vss_policy_sample_grouped(void* stream, int64_t rows, int32_t n_act, const float* mean, const vss_actor_groups* g,
+                              uint64_t seed, uint64_t counter, float* action_out) {
+  if (int rc = check_groups(rows, n_act, g, false)) return rc;
+  if (!mean) return VSS_E_ARG;
+  if (rows == 0) return VSS_OK;
+  if (!rows_fit(rows, g)) return VSS_E_ARG;
+  vpol::SampleGroups t;
+  t.group_rows = g->group_rows;
+  for (int i = 0; i < VSS_MAX_ACTOR_GROUPS; ++i) t.logstd[i] = i < g->count ? g->logstd[i] : nullptr;
+  const dim3 grid((unsigned)((rows + 255) / 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (n_act == 2) hipLaunchKernelGGL(vpol::sample_grouped_kernel<2>, grid, block, 0, s, rows, mean, t, seed, counter, action_out);
+  else hipLaunchKernelGGL(vpol::sample_grouped_kernel<6>, grid, block, 0, s, rows, mean, t, seed, counter, action_out);
   return hipGetLastError() == hipSuccess ? VSS_OK : VSS_E_LAUNCH;
 }
 

@@ -1469,6 +1469,51 @@ __global__ __launch_bounds__(256) void episode_stats_kernel(int64_t rows, const 
   ep_len[i] = (int32_t)(l * keep);
 }
 
+// Match results per opponent group (vss_match_tally), one field per lane.  A wave adds up the finished
+// fields of each group it holds (one group, unless a group boundary falls inside its 64 fields) and one
+// lane adds the four sums to the group's counters: 64-bit integer adds, exact in any order.
+__global__ __launch_bounds__(256) void match_tally_kernel(int64_t n_fields, int rows_per_field, int64_t group_fields,
+                                                          const float4* __restrict__ rew,
+                                                          const int64_t* __restrict__ dones,
+                                                          const float* __restrict__ progress_f,
+                                                          unsigned long long* tally) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  bool done = false;
+  int q = 0;
+  float goal = 0.0f;
+  long long steps = 0;
+  if (f < n_fields) {
+    const int64_t r = f * rows_per_field;
+    done = dones[r] != 0;
+    if (done) {
+      q = (int)(f / group_fields);
+      goal = rew[r].x;
+      steps = (long long)progress_f[r];
+    }
+  }
+  unsigned long long todo = __ballot(done);
+  while (todo) {  // uniform over the wave: one turn per group present among its finished fields
+    const int leader = __ffsll(todo) - 1;
+    const int qq = __shfl(q, leader);
+    const bool mine = done && q == qq;
+    const unsigned long long m = __ballot(mine);
+    const unsigned long long won = __ballot(mine && goal > 0.0f);
+    const unsigned long long lost = __ballot(mine && goal < 0.0f);
+    long long s = mine ? steps : 0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d);
+    if (lane == leader) {
+      unsigned long long* t = tally + 4 * qq;
+      atomicAdd(t + 0, (unsigned long long)__popcll(m));
+      if (won) atomicAdd(t + 1, (unsigned long long)__popcll(won));
+      if (lost) atomicAdd(t + 2, (unsigned long long)__popcll(lost));
+      atomicAdd(t + 3, (unsigned long long)s);
+    }
+    todo &= ~m;
+  }
+}
+
 }  // namespace vss
 
 // ================================================================================================
@@ -1632,6 +1677,21 @@ int vss_episode_stats(void* stream, int64_t rows, const float* rews, const int64
   hipLaunchKernelGGL(vss::episode_stats_kernel, grid, block, 0, (hipStream_t)stream, rows,
                      reinterpret_cast<const float4*>(rews), dones, reinterpret_cast<float4*>(ep_returns), ep_lengths,
                      reinterpret_cast<float4*>(returned_returns), returned_lengths, return_sum);
+  return launch_status();
+}
+
+int vss_match_tally(void* stream, int64_t n_fields, int32_t rows_per_field, int64_t group_fields, int32_t count,
+                    const float* rew, const int64_t* dones, const float* progress_f, int64_t* tally) {
+  if (n_fields < 0 || n_fields > (int64_t(1) << 29) || !(rows_per_field == 1 || rows_per_field == 3) ||
+      group_fields <= 0 || count < 1 || count > VSS_MAX_ACTOR_GROUPS)
+    return VSS_E_ARG;
+  if ((n_fields + count - 1) / count > group_fields) return VSS_E_ARG;  // count * group_fields < n_fields
+  if (bad(rew, 16) || bad(dones, 8) || bad(progress_f, 4) || bad(tally, 8)) return VSS_E_ARG;
+  if (n_fields == 0) return VSS_OK;
+  const dim3 grid((unsigned)((n_fields + 255) / 256)), block(256);
+  hipLaunchKernelGGL(vss::match_tally_kernel, grid, block, 0, (hipStream_t)stream, n_fields, (int)rows_per_field,
+                     group_fields, reinterpret_cast<const float4*>(rew), dones, progress_f,
+                     reinterpret_cast<unsigned long long*>(tally));
   return launch_status();
 }
 

@@ -57,8 +57,8 @@ def make_env(args):
                virtual_screen_capture=getattr(args, "capture_video", False), force_render=False)
     wrappers = {"sa": SingleAgent, "cma": CMA, "dma": DMA}
     opponent = getattr(args, "opponent", "ou")
-    if opponent != "ou" and not (opponent == "self" or os.path.exists(opponent)):
-        raise ValueError(f"--opponent must be ou, self or a checkpoint path, got {opponent!r}")
+    if opponent != "ou" and not (opponent in ("self", "pool") or os.path.exists(opponent)):
+        raise ValueError(f"--opponent must be ou, self, pool or a checkpoint path, got {opponent!r}")
     # the opponent itself (a snapshot of the Agent) is set by the train loop: set_opponent()
     return envs, wrappers[args.env_id](envs)
 
@@ -145,6 +145,8 @@ class _FusedWrapper(Wrapper):
         """Drive the yellow team with `team` -- play.py's protocol, team(act (N,3,2) written in place,
         obs (N,3,52)) -- inside the fused step (vss_step_versus) instead of OU noise; None (the
         default) restores the OU opponent and step() is the plain path again."""
+        if team is not None and hasattr(team, "check_env"):
+            team.check_env(self.env)  # e.g. OpponentPool: the field count and a positive goal weight
         self._opponent = team
         if team is None:
             return
@@ -176,6 +178,9 @@ class _FusedWrapper(Wrapper):
             self._opponent(self._opp_act, self._opp_obs)
             env.native_step_versus(self.MODE, action, io, self._opp_act, self._opp_obs)
             infos["opponent_obs"] = self._opp_obs
+            if hasattr(self._opponent, "observe"):  # a league counts the finished fields' results per slot
+                self._opponent.observe(self._rews, env.reset_buf if self._dones is None else self._dones,
+                                       self._progress)
         dones = env.reset_buf if self._dones is None else self._dones
         return {"obs": self._obs}, self._reward, dones, infos
 

@@ -21,8 +21,9 @@ the loop -- and the machinery under it lives in vss_amd/:
 * no per-element host-synchronising logging loop (ppo…:273-279): episode statistics are
   reduced on the device and read once per update;
 * logging is optional (TensorBoard if installed, else a CSV of the same scalars; no W&B);
-* `--opponent self|PATH` (a build addition): the yellow team is a policy -- a snapshot of the learner, refreshed
-  every `--opponent-update-every` updates, or a checkpoint -- instead of OU noise (vss_amd/opponent.py).
+* `--opponent self|pool|PATH` (a build addition): the yellow team is a policy -- a snapshot of the learner, refreshed
+  every `--opponent-update-every` updates, a league of past snapshots (OpponentPool), or a checkpoint -- instead
+  of OU noise (vss_amd/opponent.py).
 """
 from __future__ import annotations
 
@@ -119,11 +120,19 @@ def parse_args(argv=None):
                         "args.kernel_warmup_s); the training itself is unchanged")
     p.add_argument("--opponent", type=str, default="ou",
                    help="the yellow team: 'ou' (Ornstein-Uhlenbeck noise, the reference's wrappers), 'self' (a frozen "
-                        "snapshot of the learner's actor, vss_amd.opponent.SnapshotOpponent, inside the fused step) or "
-                        "the path of an agent checkpoint in the reference's format (a fixed opponent)")
+                        "snapshot of the learner's actor, vss_amd.opponent.SnapshotOpponent, inside the fused step), "
+                        "'pool' (a league of past snapshots, vss_amd.opponent.OpponentPool) or the path of an agent "
+                        "checkpoint in the reference's format (a fixed opponent)")
     p.add_argument("--opponent-update-every", type=int, default=1,
                    help="--opponent self: copy the learner's weights into the snapshot after every K-th update "
-                        "(0: keep the initial weights)")
+                        "(0: keep the initial weights); --opponent pool: add a snapshot to the pool every K-th update")
+    p.add_argument("--opponent-pool-size", type=int, default=16, help="--opponent pool: snapshots kept (the oldest leaves)")
+    p.add_argument("--opponent-pool-slots", type=int, default=8,
+                   help="--opponent pool: slices of the fields, each playing one snapshot (at most 16)")
+    p.add_argument("--opponent-pool-latest", type=float, default=0.5,
+                   help="--opponent pool: the share of the slots that plays the newest snapshot")
+    p.add_argument("--opponent-pfsp-power", type=float, default=1.0,
+                   help="--opponent pool: the other slots draw a snapshot with probability ~ (1 - win rate) ** power")
     args = p.parse_args(argv)
     args.batch_size = int(args.num_envs * args.num_steps)
     args.minibatch_size = int(args.batch_size // args.num_minibatches)
@@ -388,7 +397,22 @@ def train(args, on_update=None):
     # The weights are the same on every rank, so sync() is a local copy (no collective).
     opponent = None
     opponent_mode = getattr(args, "opponent", "ou")
-    if opponent_mode != "ou":
+    # 'pool': a league of past snapshots (OpponentPool), each on its slice of this rank's fields; the weights are
+    # equal on every rank, the match tallies -- and so the assignments -- are per rank (no collective either).
+    if opponent_mode == "pool":
+        from vss_amd.opponent import KIND_OF_ENV, OpponentPool
+        opponent = OpponentPool(agent, KIND_OF_ENV[args.env_id], unwrapped_env.num_fields,
+                                slots=getattr(args, "opponent_pool_slots", 8),
+                                capacity=getattr(args, "opponent_pool_size", 16),
+                                latest=getattr(args, "opponent_pool_latest", 0.5),
+                                pfsp_power=getattr(args, "opponent_pfsp_power", 1.0), seed=seed * 7919 + 104729)
+        fused_env.set_opponent(opponent)
+        if getattr(args, "kernel_warmup", False):
+            # outside the clock: the pool's forward at this run's row count; the Philox counter is put back
+            counter = opponent.counter
+            opponent(torch.zeros_like(fused_env._opp_act), fused_env._opp_obs)
+            opponent.counter = counter
+    elif opponent_mode != "ou":
         from vss_amd.opponent import KIND_OF_ENV, SnapshotOpponent
         opponent = SnapshotOpponent(agent, KIND_OF_ENV[args.env_id], seed=seed * 7919 + 104729)
         if opponent_mode != "self":
@@ -508,6 +532,11 @@ def train(args, on_update=None):
                **{k: float(v) for k, v in stats.items()}}
         history.append(rec)
         every = getattr(args, "opponent_update_every", 1)
+        if opponent_mode == "pool":
+            # the snapshots this update's rollout played and the learner's result against each, per slot; then one
+            # host read of the device tally, a new snapshot on every K-th update, and the slots are dealt again
+            rec["opponent_pool_versions"] = opponent.versions
+            rec["opponent_pool_winrate"] = opponent.end_update(agent, update, every)["winrate"]
         if opponent is not None and opponent_mode == "self" and every > 0 and update % every == 0:
             opponent.sync(agent, version=update)
         for k, name in (("v_loss", "value_loss"), ("pg_loss", "policy_loss"), ("entropy", "entropy"),

@@ -50,7 +50,8 @@ STATE_CHANNELS = 58
 CH_BALL_X, CH_BALL_Y, CH_BALL_VX, CH_BALL_VY = 0, 1, 2, 3
 CH_RX, CH_RY, CH_RQX, CH_RQY, CH_RQZ, CH_RQW, CH_RVX, CH_RVY, CH_RW = 4, 10, 16, 22, 28, 34, 40, 46, 52
 EXPORTED = ("vss_abi_version", "vss_source_hash", "vss_error_string", "vss_step", "vss_step_replay", "vss_step_versus",
-            "vss_actor_forward", "vss_rollout", "vss_reset_dones",
+            "vss_actor_forward", "vss_actor_forward_grouped", "vss_policy_sample_grouped", "vss_match_tally",
+            "vss_rollout", "vss_reset_dones",
             "vss_reset_dones_replay",
             "vss_compute_observations", "vss_mlp_packed_size", "vss_mlp_pack", "vss_policy_forward",
             "vss_value_forward_masked", "vss_policy_sample", "vss_episode_stats", "vss_tanh_grad_chunks", "vss_tanh_grad_bias",
@@ -92,6 +93,15 @@ class VssStepIO(ctypes.Structure):
 class VssVersusIO(ctypes.Structure):
     """The yellow team's side of vss_step_versus (include/vss.h vss_versus_io)."""
     _fields_ = [(k, ctypes.c_void_p) for k in ("opp_actions", "opp_obs")]
+
+
+MAX_ACTOR_GROUPS = 16
+
+
+class VssActorGroups(ctypes.Structure):
+    """Per-group actors of the grouped entries (include/vss.h vss_actor_groups)."""
+    _fields_ = [("count", ctypes.c_int32), ("group_rows", ctypes.c_int64),
+                ("actor_packed", ctypes.c_void_p * MAX_ACTOR_GROUPS), ("logstd", ctypes.c_void_p * MAX_ACTOR_GROUPS)]
 
 
 class VssRolloutIO(ctypes.Structure):
@@ -177,6 +187,12 @@ def load() -> ctypes.CDLL:
     L.vss_actor_forward.restype = ctypes.c_int
     L.vss_policy_sample.argtypes = [P, i64, i32, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P, P, P]
     L.vss_policy_sample.restype = ctypes.c_int
+    L.vss_actor_forward_grouped.argtypes = [P, i64, i32, P, P, ctypes.c_uint64, ctypes.c_uint64, P, P]
+    L.vss_actor_forward_grouped.restype = ctypes.c_int
+    L.vss_policy_sample_grouped.argtypes = [P, i64, i32, P, P, ctypes.c_uint64, ctypes.c_uint64, P]
+    L.vss_policy_sample_grouped.restype = ctypes.c_int
+    L.vss_match_tally.argtypes = [P, i64, i32, i64, i32, P, P, P, P]
+    L.vss_match_tally.restype = ctypes.c_int
     L.vss_episode_stats.argtypes = [P, i64] + [P] * 7
     L.vss_episode_stats.restype = ctypes.c_int
     L.vss_tanh_grad_chunks.argtypes = [i64, i32]
