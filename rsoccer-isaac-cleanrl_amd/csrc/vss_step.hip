@@ -14,6 +14,12 @@
 //   6. stores state, bookkeeping and the AoS reward block (LDS transpose again).
 // Everything is float32 with FMA contraction disabled (-ffp-contract=off and the pragma
 // below): results are bit-identical to the CPU oracle (oracle/vss_oracle.c).
+//
+// The step exists once: step_body<MODE, REPLAY, VERSUS>.  step_kernel<MODE, REPLAY> (vss_step,
+// vss_step_replay) and step_versus_kernel<MODE> (vss_step_versus) are its two __global__ entries;
+// what the versus step does differently sits under `if constexpr (VERSUS)`.  rollout_kernel keeps
+// its own pipelined copy of steps 3-4 and shares the reset (reset_if_done).  On the host,
+// check_step_io and launch_step serve all three step entries.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
@@ -872,7 +878,36 @@ __device__ __forceinline__ void ou_noise_split(float a[12], uint32_t k0, uint32_
   for (int k = NL; k < 12; ++k) a[k] = clampf((a[k] - K_OU_THETA * a[k]) + z[k], -1.0f, 1.0f);
 }
 
-// ---- the step kernel -------------------------------------------------------------------------------
+// The versus step's OU update (SA only): blue robots 1-2 (slots 2..5) keep the normals
+// ou_noise_split<SA> gives those slots -- Philox (field, ctr, OU purpose), block 0 words 2-3 (slots
+// 2, 3) and block 1 words 0-1 (slots 4, 5), one Box-Muller pair per lane half here -- so the four
+// values equal vss_step(SA)'s bit for bit.  The yellow slots come from the caller.
+__device__ __forceinline__ void ou_noise_blue_sa(float a[12], uint32_t k0, uint32_t k1, uint32_t field, uint32_t ctr) {
+  const bool up = threadIdx.x >= 32;
+  uint32_t w[4];
+  philox(k0, k1, field, ctr, kPurposeOU << 24, up ? 1u : 0u, w);
+  float zc, zs, z[6];
+  box_muller(up ? w[0] : w[2], up ? w[1] : w[3], zc, zs);  // lower: slots 2,3   upper: 4,5
+  exch(zc, z[2], z[4]);
+  exch(zs, z[3], z[5]);
+#pragma unroll
+  for (int k = 2; k < 6; ++k) a[k] = clampf((a[k] - K_OU_THETA * a[k]) + z[k], -1.0f, 1.0f);
+}
+
+// reset_dones (envs/vss.py:202, 267-333): `dof` = the clamped actions, zeroed where the field is re-sampled.
+template <bool REPLAY>
+__device__ __forceinline__ void reset_if_done(bool valid, int64_t done, const ResetDraws& rd, Bodies& b,
+                                              const float a[12], float dof[12]) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) dof[k] = a[k];
+  if (valid && done) {
+    reset_field_split<REPLAY>(b, rd);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dof[k] = dof[k] * 0.0f;
+  }
+}
+
+// ---- the step kernels --------------------------------------------------------------------------------
 // One wave's inputs (kFpw fields), all issued at the start of the kernel: the field's bookkeeping and
 // 46 live state channels, and the wave's contiguous AoS blocks of the batch's 12-float action rows
 // (FULL) or OU buffer rows (wrapped) and learner action rows (wrapped).
@@ -894,9 +929,6 @@ struct StepArgs {
   uint32_t nt_obs;      // FULL: stream obs with nontemporal stores (footprint past the Infinity Cache)
 };
 
-// REPLAY = false: the product kernel (Philox draws).  REPLAY = true: the parity entry
-// vss_step_replay, the same kernel consuming recorded reference draws (ResetDraws above; OU
-// normals from rd.normals) -- every other instruction is shared.
 template <int MODE>
 __device__ __forceinline__ void load_batch(const StepArgs& args, int64_t f0, int nv, int fl, int lane, BatchIn& in) {
   constexpr int NL = MODE == VSS_MODE_SA ? 2 : 6;
@@ -914,16 +946,32 @@ __device__ __forceinline__ void load_batch(const StepArgs& args, int64_t f0, int
   if constexpr (MODE != VSS_MODE_FULL) prefetch_lrn<NL>(args.io.actions + f0 * NL, nv, lane, in.lrn);
 }
 
-template <int MODE, bool REPLAY = false>
-__global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
+// The body of step_kernel<MODE, REPLAY> (VERSUS = false) and of step_versus_kernel<MODE> (VERSUS =
+// true).  The versus step is the wrapped step with the yellow slots 6..11 read from vs.opp_actions
+// instead of the OU process, and the yellow robots' observations after the reset (rows [:, 1] of
+// FULL's obs) written to vs.opp_obs for the opponent's next decision; every vss_step_io output keeps
+// its meaning.  What differs sits under `if constexpr (VERSUS)`:
+//   * the observation records carry the mirror slots (kRecObs6, the LDS of the FULL instantiation);
+//   * the wave's (nv, 6) opponent action rows are prefetched with the other inputs and staged with
+//     the learner's rows;
+//   * OU noise: SA keeps it for blue robots 1-2 only (ou_noise_blue_sa), CMA / DMA draw none;
+//   * the terminal record skips the mirror slots (the learner's rows only), the record after the
+//     reset has them, and serves two streams: the learner's block and the yellow team's;
+//   * ou_buf afterwards holds all twelve applied, pre-clamp actions.
+// Both observation streams of a wrapped mode are nontemporal, versus or not.
+template <int MODE, bool REPLAY, bool VERSUS>
+__device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus_io& vs) {
+  static_assert(!VERSUS || (!REPLAY && (MODE == VSS_MODE_SA || MODE == VSS_MODE_CMA || MODE == VSS_MODE_DMA)),
+                "versus: wrapped modes only, no replay");
   constexpr int A = MODE == VSS_MODE_FULL ? 6 : (MODE == VSS_MODE_DMA ? 3 : 1);
   constexpr int R = MODE == VSS_MODE_DMA ? 3 : 1;
   constexpr int NL = MODE == VSS_MODE_SA ? 2 : 6;  // learner action floats per field
+  constexpr int REC = VERSUS ? kRecObs6 : obs_rec<A>();  // observation record stride
   // lanes L and L + 32 hold field L (physics_split); lanes < 32 address the LDS records, so LDS holds
   // 32 plain records or kFpw observation records, whichever is larger
   static_assert(2 * kFpw == kWave, "two lanes per field");
-  constexpr int kLds = 32 * kRec > kFpw * obs_rec<A>() ? 32 * kRec : kFpw * obs_rec<A>();
-  static_assert(kFpw * obs_rec<A>() <= kLds, "observation records must fit the LDS block");
+  constexpr int kLds = 32 * kRec > kFpw * REC ? 32 * kRec : kFpw * REC;
+  static_assert(kFpw * REC <= kLds, "observation records must fit the LDS block");
   __shared__ float lds[kLds + kTabWords];
   uint32_t* tab = reinterpret_cast<uint32_t*>(lds + kLds);
   stage_obs_table(tab, threadIdx.x);
@@ -934,21 +982,24 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
   const bool writer = lane < 32;   // writes the field's LDS record slots
   const uint32_t k0 = (uint32_t)args.p.seed, k1 = (uint32_t)(args.p.seed >> 32);
   float* rec = lds + fl * kRec;
-  float* orec = lds + lane * obs_rec<A>();  // observation record (lanes < kFpw)
+  float* orec = lds + lane * REC;  // observation record (lanes < kFpw)
 
   const int64_t f0 = (int64_t)blockIdx.x * kFpw;
   const int nv = (int)(n - f0 < kFpw ? n - f0 : kFpw);
   BatchIn cur;
   load_batch<MODE>(args, f0, nv, fl, lane, cur);
+  float2 opp[2];  // versus: the wave's (nv, 6) opponent action rows, with the other inputs
+  if constexpr (VERSUS) prefetch_lrn<6>(vs.opp_actions + f0 * 6, nv, lane, opp);
   const int64_t f = f0 + fl;
   const bool valid = fl < nv;
   const bool owner = valid && writer;  // stores the field's outputs
 
-  int64_t progress = cur.progress, reset_prev = cur.reset_prev;
-  uint32_t ctr = cur.ctr;
+  int64_t progress = cur.progress;
+  const uint32_t ctr = cur.ctr;
   Bodies b = cur.b;
 
-  // -- actions: FULL reads (N,12); wrapped modes read + update the OU action buffer --------------
+  // -- actions: FULL reads (N,12); wrapped modes read + update the OU action buffer, then take the
+  //    learner's slots (and, versus, the opponent's) --------------------------------------------------
   float a[12];
   stage12(cur.blk, nv, lds, lane);
   __syncthreads();
@@ -956,10 +1007,13 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
   for (int k = 0; k < 12; ++k) a[k] = rec[k];
   __syncthreads();
 
+  float ou[12];  // wrapped: the applied, pre-clamp actions -- what ou_buf holds after the call
   if constexpr (MODE != VSS_MODE_FULL) {
     // random_ou (envs/wrappers.py:5-19): a <- clamp(a - 0.1 a + N(0, 0.15^2), -1, 1); the learner
     // slots (pairs 0 for SA, 0..2 for CMA/DMA) are overwritten, so their normals are not needed.
-    if constexpr (REPLAY) {
+    if constexpr (VERSUS) {
+      if constexpr (MODE == VSS_MODE_SA) ou_noise_blue_sa(a, k0, k1, (uint32_t)f, ctr);
+    } else if constexpr (REPLAY) {
       // torch.normal(0, 0.15, (N, 2, 3, 2)) of random_ou: the field's 12 recorded samples
       if (valid) {
         const float* z = args.rd.normals + f * 12;
@@ -970,13 +1024,15 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
       ou_noise_split<MODE>(a, k0, k1, (uint32_t)f, ctr);
     }
     stage_lrn<NL>(cur.lrn, nv, lds, lane);
+    if constexpr (VERSUS) stage_lrn<6>(opp, nv, lds + 6, lane);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < NL; ++k) a[k] = rec[k];
+    if constexpr (VERSUS) {
+#pragma unroll
+      for (int k = 6; k < 12; ++k) a[k] = rec[k];
+    }
     __syncthreads();
-  }
-  float ou[12];
-  if constexpr (MODE != VSS_MODE_FULL) {
 #pragma unroll
     for (int k = 0; k < 12; ++k) ou[k] = a[k];
   }
@@ -985,7 +1041,7 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
   const float clip = args.p.clip_actions;
 #pragma unroll
   for (int k = 0; k < 12; ++k) a[k] = clampf(a[k], -clip, clip);
-  if (reset_prev != 0) progress = 0;
+  if (cur.reset_prev != 0) progress = 0;
 
   float pbx = b.bx, pby = b.by, prx[6], pry[6];
 #pragma unroll
@@ -1007,25 +1063,20 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
   // -- terminal observation (envs/vss.py:195-196) ----------------------------------------------------------
   if (lane < kFpw) write_obs_record<A>(orec, b, a);
   __syncthreads();
-  coop_store_obs<A>(args.io.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL);
+  coop_store_obs<A, 0, REC>(args.io.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL);
   __syncthreads();
 
   // -- reset_dones (envs/vss.py:202, 267-333) ---------------------------------------------------------------
   float dof[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) dof[k] = a[k];
-  if (valid && done) {
-    const ResetDraws rd{k0, k1, (uint32_t)f, ctr, 0u, REPLAY ? args.rd.uniforms + f * args.rd.uniform_stride : nullptr,
-                        REPLAY ? args.rd_rounds : (uint32_t)kMaxRejectRounds};
-    reset_field_split<REPLAY>(b, rd);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) dof[k] = dof[k] * 0.0f;
-  }
+  const ResetDraws rd{k0, k1, (uint32_t)f, ctr, 0u, REPLAY ? args.rd.uniforms + f * args.rd.uniform_stride : nullptr,
+                      REPLAY ? args.rd_rounds : (uint32_t)kMaxRejectRounds};
+  reset_if_done<REPLAY>(valid, done, rd, b, a, dof);
 
-  // -- observation after reset (envs/vss.py:203) -------------------------------------------------------------
-  if (lane < kFpw) write_obs_record<A>(orec, b, dof);
+  // -- observation after reset (envs/vss.py:203); versus: the yellow team's block from the same record -------
+  if (lane < kFpw) write_obs_record<VERSUS ? 6 : A>(orec, b, dof);
   __syncthreads();
-  coop_store_obs<A>(args.io.obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL || args.nt_obs != 0);
+  coop_store_obs<A, 0, REC>(args.io.obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL || args.nt_obs != 0);
+  if constexpr (VERSUS) coop_store_obs<3, 3, REC>(vs.opp_obs + f0 * (52 * 3), nv, lds, tab, lane, true);
   __syncthreads();
 
   // -- bookkeeping --------------------------------------------------------------------------------------------
@@ -1103,185 +1154,18 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
   }
 }
 
-// ---- the versus step: a caller-supplied buffer drives the yellow team ---------------------------------
-// step_kernel<MODE> (SA / CMA / DMA) with the yellow slots 6..11 read from vs.opp_actions instead of
-// the OU process, and the yellow robots' observations after the reset (rows [:, 1] of FULL's obs)
-// written to vs.opp_obs for the opponent's next decision.  Every vss_step_io output keeps the
-// meaning it has in step_kernel<MODE>; the device functions are shared, so the physics, rewards,
-// resets and observation records are the same operation sequences.  The observation records carry
-// the mirror slots (kRecObs6, the LDS of the FULL instantiation); the learner's block and the
-// opponent's stream out of the same record, both nontemporal.
-//
-// SA: blue robots 1-2 (slots 2..5) keep the OU update with the normals ou_noise_split<SA> gives
-// them -- Philox (field, ctr, OU purpose), block 0 words 2-3 (slots 2, 3) and block 1 words 0-1
-// (slots 4, 5), one Box-Muller pair per lane half here -- so the four values equal vss_step(SA)'s
-// bit for bit.  CMA / DMA draw no OU noise.
+// REPLAY = false: the product kernel (Philox draws).  REPLAY = true: the parity entry
+// vss_step_replay, the same kernel consuming recorded reference draws (ResetDraws above; OU
+// normals from rd.normals) -- every other instruction is shared.
+template <int MODE, bool REPLAY = false>
+__global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
+  step_body<MODE, REPLAY, false>(args, vss_versus_io{});
+}
+
+// The versus step (vss_step_versus): a caller-supplied buffer drives the yellow team.
 template <int MODE>
 __global__ __launch_bounds__(kWave) void step_versus_kernel(StepArgs args, vss_versus_io vs) {
-  static_assert(MODE == VSS_MODE_SA || MODE == VSS_MODE_CMA || MODE == VSS_MODE_DMA, "wrapped modes only");
-  constexpr int A = MODE == VSS_MODE_DMA ? 3 : 1;
-  constexpr int R = MODE == VSS_MODE_DMA ? 3 : 1;
-  constexpr int NL = MODE == VSS_MODE_SA ? 2 : 6;  // learner action floats per field
-  static_assert(2 * kFpw == kWave, "two lanes per field");
-  constexpr int kLds = 32 * kRec > kFpw * kRecObs6 ? 32 * kRec : kFpw * kRecObs6;
-  __shared__ float lds[kLds + kTabWords];
-  uint32_t* tab = reinterpret_cast<uint32_t*>(lds + kLds);
-  stage_obs_table(tab, threadIdx.x);
-
-  const int64_t n = args.n;
-  const int lane = threadIdx.x;
-  const int fl = lane & 31;
-  const bool writer = lane < 32;
-  const uint32_t k0 = (uint32_t)args.p.seed, k1 = (uint32_t)(args.p.seed >> 32);
-  float* rec = lds + fl * kRec;
-  float* orec = lds + lane * kRecObs6;  // observation record (lanes < kFpw)
-
-  const int64_t f0 = (int64_t)blockIdx.x * kFpw;
-  const int nv = (int)(n - f0 < kFpw ? n - f0 : kFpw);
-  BatchIn cur;
-  load_batch<MODE>(args, f0, nv, fl, lane, cur);
-  float2 opp[2];  // the wave's (nv, 6) opponent action rows, with the other inputs
-  prefetch_lrn<6>(vs.opp_actions + f0 * 6, nv, lane, opp);
-  const int64_t f = f0 + fl;
-  const bool valid = fl < nv;
-  const bool owner = valid && writer;
-
-  int64_t progress = cur.progress, reset_prev = cur.reset_prev;
-  const uint32_t ctr = cur.ctr;
-  Bodies b = cur.b;
-
-  // -- actions: the OU buffer (SA: slots 2..5 updated), then the learner's and the opponent's slots --
-  float a[12];
-  stage12(cur.blk, nv, lds, lane);
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 12; ++k) a[k] = rec[k];
-  __syncthreads();
-  if constexpr (MODE == VSS_MODE_SA) {
-    const bool up = lane >= 32;
-    uint32_t w[4];
-    philox(k0, k1, (uint32_t)f, ctr, kPurposeOU << 24, up ? 1u : 0u, w);
-    float zc, zs, z[6];
-    box_muller(up ? w[0] : w[2], up ? w[1] : w[3], zc, zs);  // lower: slots 2,3   upper: 4,5
-    exch(zc, z[2], z[4]);
-    exch(zs, z[3], z[5]);
-#pragma unroll
-    for (int k = 2; k < 6; ++k) a[k] = clampf((a[k] - K_OU_THETA * a[k]) + z[k], -1.0f, 1.0f);
-  }
-  stage_lrn<NL>(cur.lrn, nv, lds, lane);
-  stage_lrn<6>(opp, nv, lds + 6, lane);
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NL; ++k) a[k] = rec[k];
-#pragma unroll
-  for (int k = 6; k < 12; ++k) a[k] = rec[k];
-  __syncthreads();
-  float ou[12];  // the applied, pre-clamp actions: what ou_buf holds after the call
-#pragma unroll
-  for (int k = 0; k < 12; ++k) ou[k] = a[k];
-
-  const float clip = args.p.clip_actions;
-#pragma unroll
-  for (int k = 0; k < 12; ++k) a[k] = clampf(a[k], -clip, clip);
-  if (reset_prev != 0) progress = 0;
-
-  float pbx = b.bx, pby = b.by, prx[6], pry[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) { prx[i] = b.x[i]; pry[i] = b.y[i]; }
-
-  if (valid) physics_split(b, a);
-
-  progress += 1;
-  float rew[24];
-  const int64_t done = rewards_and_done(args.p, b, pbx, pby, prx, pry, a, progress, rew);
-
-  wait_loads();  // every load retired before the first store (see step_kernel)
-
-  // -- terminal observation: the learner's rows only (no mirror slots needed) -------------------------
-  if (lane < kFpw) write_obs_record<A>(orec, b, a);
-  __syncthreads();
-  coop_store_obs<A, 0, kRecObs6>(args.io.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, true);
-  __syncthreads();
-
-  float dof[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) dof[k] = a[k];
-  if (valid && done) {
-    const ResetDraws rd{k0, k1, (uint32_t)f, ctr, 0u, nullptr, (uint32_t)kMaxRejectRounds};
-    reset_field_split<false>(b, rd);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) dof[k] = dof[k] * 0.0f;
-  }
-
-  // -- observations after the reset: the learner's block and the yellow team's, from one record -------
-  if (lane < kFpw) write_obs_record<6>(orec, b, dof);
-  __syncthreads();
-  coop_store_obs<A, 0, kRecObs6>(args.io.obs + f0 * (52 * A), nv, lds, tab, lane, true);
-  coop_store_obs<3, 3, kRecObs6>(vs.opp_obs + f0 * (52 * 3), nv, lds, tab, lane, true);
-  __syncthreads();
-
-  // -- bookkeeping ---------------------------------------------------------------------------------------
-  const uint8_t time_out = (progress >= (int64_t)args.p.max_episode_length - 1) && done != 0;
-  if (owner) {
-    const uint32_t ufl = (uint32_t)fl;
-    store_bodies(args.s.state, n, f0, fl, b);
-    at(args.s.progress_buf + f0, 8u * ufl) = progress;
-    at(args.s.reset_buf + f0, 8u * ufl) = done;
-    at(args.s.rng_counter + f0, 4u * ufl) = ctr + 1u;
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-      at(args.io.time_outs + f0 * R, (uint32_t)(ufl * R + k)) = time_out;
-      at(args.io.progress_f + f0 * R, 4u * (ufl * R + k)) = (float)progress;
-    }
-    if constexpr (MODE == VSS_MODE_DMA) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) at(args.io.dones_rep + f0 * 3, 8u * (ufl * 3 + k)) = done;
-    }
-  }
-
-  if (writer) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) rec[k] = dof[k];
-  }
-  __syncthreads();
-  coop_store<12>(args.s.dof_velocity_buf + f0 * 12, nv, lds, lane);
-  __syncthreads();
-  if (writer) {
-#pragma unroll
-    for (int k = 0; k < 12; ++k) rec[k] = done ? ou[k] * 0.0f : ou[k];
-  }
-  __syncthreads();
-  coop_store<12>(args.io.ou_buf + f0 * 12, nv, lds, lane);
-  __syncthreads();
-
-  // rewards, as step_kernel<MODE>
-  if constexpr (MODE == VSS_MODE_SA) {
-    if (owner) {
-      at(reinterpret_cast<float4*>(args.io.rew) + f0, 16u * (uint32_t)fl) = make_float4(rew[0], rew[1], rew[2], rew[3]);
-      at(args.io.reward_sum + f0, 4u * (uint32_t)fl) = ((rew[0] + rew[1]) + rew[2]) + rew[3];
-    }
-  } else if constexpr (MODE == VSS_MODE_CMA) {
-    if (owner) {
-      float m[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) m[c] = ((rew[c] + rew[4 + c]) + rew[8 + c]) / 3.0f;
-      at(reinterpret_cast<float4*>(args.io.rew) + f0, 16u * (uint32_t)fl) = make_float4(m[0], m[1], m[2], m[3]);
-      at(args.io.reward_sum + f0, 4u * (uint32_t)fl) = ((m[0] + m[1]) + m[2]) + m[3];
-    }
-  } else {
-    if (writer) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) rec[k] = rew[k];
-    }
-    __syncthreads();
-    coop_store<12>(args.io.rew + f0 * 12, nv, lds, lane);
-    if (owner) {
-#pragma unroll
-      for (int ag = 0; ag < 3; ++ag)
-        at(args.io.reward_sum + f0 * 3, 4u * ((uint32_t)fl * 3 + ag)) =
-            ((rew[4 * ag] + rew[4 * ag + 1]) + rew[4 * ag + 2]) + rew[4 * ag + 3];
-    }
-  }
+  step_body<MODE, false, true>(args, vs);
 }
 
 // ---- K control steps per launch (open-loop action sequences) -----------------------------------------
@@ -1359,14 +1243,8 @@ __global__ __launch_bounds__(kWave) void rollout_kernel(RolloutArgs args) {
     __syncthreads();
     coop_store_obs<6>(args.io.terminal_obs + (step_off + f0) * 312, nv, lds, tab, lane, true);  // K steps: past the cache
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 12; ++i) dof[i] = a[i];
-    if (valid && done) {
-      const ResetDraws rd{k0, k1, (uint32_t)f, ctr + (uint32_t)k, 0u, nullptr, (uint32_t)kMaxRejectRounds};
-      reset_field_split<false>(b, rd);
-#pragma unroll
-      for (int i = 0; i < 12; ++i) dof[i] = dof[i] * 0.0f;
-    }
+    const ResetDraws rd{k0, k1, (uint32_t)f, ctr + (uint32_t)k, 0u, nullptr, (uint32_t)kMaxRejectRounds};
+    reset_if_done<false>(valid, done, rd, b, a, dof);
     if (lane < kFpw) write_obs_record<6>(orec, b, dof);
     __syncthreads();
     coop_store_obs<6>(args.io.obs + (step_off + f0) * 312, nv, lds, tab, lane, true);
@@ -1542,22 +1420,25 @@ static int replay_rounds(const vss_replay_draws* d) {
   return r > vss::kMaxRejectRounds ? -1 : (int)r;
 }
 
-template <bool REPLAY>
-static int step_impl(void* stream, int64_t n, int32_t mode, const vss_params* p, const vss_state* st,
-                     const vss_step_io* io, const vss_replay_draws* rd) {
-  if (int rc = check_state(n, st)) return rc;
-  if (!p || !io || mode < VSS_MODE_FULL || mode > VSS_MODE_DMA) return VSS_E_ARG;
-  if (bad(io->actions, mode == VSS_MODE_FULL ? 16 : 8) || bad(io->obs, 16) || bad(io->terminal_obs, 16) ||
-      bad(io->rew, 16) || bad(io->time_outs, 1) || bad(io->progress_f, 4) || misaligned(io->reward_sum, 4) ||
+// The vss_step_io checks of vss_step, vss_step_replay and vss_step_versus.  The wrapped modes (the
+// versus step has no other) need ou_buf and reward_sum, DMA needs dones_rep; FULL takes reward_sum
+// if given.
+static int check_step_io(int32_t mode, const vss_step_io* io) {
+  const bool wrapped = mode != VSS_MODE_FULL;
+  if (bad(io->actions, wrapped ? 8 : 16) || bad(io->obs, 16) || bad(io->terminal_obs, 16) || bad(io->rew, 16) ||
+      bad(io->time_outs, 1) || bad(io->progress_f, 4) || misaligned(io->reward_sum, 4) ||
       misaligned(io->ou_buf, 16) || misaligned(io->dones_rep, 8))
     return VSS_E_ARG;
-  if (mode != VSS_MODE_FULL && (!io->ou_buf || !io->reward_sum)) return VSS_E_ARG;
+  if (wrapped && (!io->ou_buf || !io->reward_sum)) return VSS_E_ARG;
   if (mode == VSS_MODE_DMA && !io->dones_rep) return VSS_E_ARG;
-  int rounds = 0;
-  if (REPLAY) {
-    rounds = replay_rounds(rd);
-    if (rounds < 1 || (mode != VSS_MODE_FULL && bad(rd->normals, 4))) return VSS_E_ARG;
-  }
+  return VSS_OK;
+}
+
+// The launch of a checked step: step_versus_kernel<mode> (VERSUS; `vs` given, mode wrapped) or
+// step_kernel<mode, REPLAY>.
+template <bool REPLAY, bool VERSUS>
+static int launch_step(void* stream, int64_t n, int32_t mode, const vss_params* p, const vss_state* st,
+                       const vss_step_io* io, const vss_replay_draws* rd, int rounds, const vss_versus_io* vs) {
   if (n == 0) return VSS_OK;
   // FULL: the observation stream nontemporal once the step's footprint (3,101 B per field) is past
   // the 256 MiB Infinity Cache (coop_store_obs)
@@ -1565,19 +1446,39 @@ static int step_impl(void* stream, int64_t n, int32_t mode, const vss_params* p,
   vss::StepArgs args{n, *p, *st, *io, REPLAY ? *rd : vss_replay_draws{}, (uint32_t)rounds, nt_obs};
   const dim3 grid((unsigned)((n + vss::kFpw - 1) / vss::kFpw)), block(vss::kWave);
   hipStream_t s = (hipStream_t)stream;
+  auto launch = [&](auto m) {
+    constexpr int MODE = decltype(m)::value;
+    if constexpr (VERSUS) hipLaunchKernelGGL((vss::step_versus_kernel<MODE>), grid, block, 0, s, args, *vs);
+    else hipLaunchKernelGGL((vss::step_kernel<MODE, REPLAY>), grid, block, 0, s, args);
+  };
   switch (mode) {
-    case VSS_MODE_FULL: hipLaunchKernelGGL((vss::step_kernel<VSS_MODE_FULL, REPLAY>), grid, block, 0, s, args); break;
-    case VSS_MODE_SA: hipLaunchKernelGGL((vss::step_kernel<VSS_MODE_SA, REPLAY>), grid, block, 0, s, args); break;
-    case VSS_MODE_CMA: hipLaunchKernelGGL((vss::step_kernel<VSS_MODE_CMA, REPLAY>), grid, block, 0, s, args); break;
-    default: hipLaunchKernelGGL((vss::step_kernel<VSS_MODE_DMA, REPLAY>), grid, block, 0, s, args); break;
+    case VSS_MODE_FULL:
+      if constexpr (!VERSUS) launch(std::integral_constant<int, VSS_MODE_FULL>{});
+      break;
+    case VSS_MODE_SA: launch(std::integral_constant<int, VSS_MODE_SA>{}); break;
+    case VSS_MODE_CMA: launch(std::integral_constant<int, VSS_MODE_CMA>{}); break;
+    default: launch(std::integral_constant<int, VSS_MODE_DMA>{}); break;
   }
   return launch_status();
+}
+
+template <bool REPLAY>
+static int step_impl(void* stream, int64_t n, int32_t mode, const vss_params* p, const vss_state* st,
+                     const vss_step_io* io, const vss_replay_draws* rd) {
+  if (int rc = check_state(n, st)) return rc;
+  if (!p || !io || mode < VSS_MODE_FULL || mode > VSS_MODE_DMA) return VSS_E_ARG;
+  if (int rc = check_step_io(mode, io)) return rc;
+  int rounds = 0;
+  if (REPLAY) {
+    rounds = replay_rounds(rd);
+    if (rounds < 1 || (mode != VSS_MODE_FULL && bad(rd->normals, 4))) return VSS_E_ARG;
+  }
+  return launch_step<REPLAY, false>(stream, n, mode, p, st, io, rd, rounds, nullptr);
 }
 
 extern "C" {
 
 int vss_abi_version(void) { return VSS_ABI_VERSION; }
-
 
 const char* vss_error_string(int code) {
   switch (code) {
@@ -1602,21 +1503,9 @@ int vss_step_versus(void* stream, int64_t n, int32_t mode, const vss_params* p, 
                     const vss_step_io* io, const vss_versus_io* vs) {
   if (int rc = check_state(n, st)) return rc;
   if (!p || !io || !vs || mode < VSS_MODE_SA || mode > VSS_MODE_DMA) return VSS_E_ARG;  // FULL takes all 12 itself
-  if (bad(io->actions, 8) || bad(io->ou_buf, 16) || bad(io->obs, 16) || bad(io->terminal_obs, 16) || bad(io->rew, 16) ||
-      bad(io->reward_sum, 4) || bad(io->time_outs, 1) || bad(io->progress_f, 4) || misaligned(io->dones_rep, 8) ||
-      bad(vs->opp_actions, 8) || bad(vs->opp_obs, 16))
-    return VSS_E_ARG;
-  if (mode == VSS_MODE_DMA && !io->dones_rep) return VSS_E_ARG;
-  if (n == 0) return VSS_OK;
-  vss::StepArgs args{n, *p, *st, *io, vss_replay_draws{}, 0u, 0u};
-  const dim3 grid((unsigned)((n + vss::kFpw - 1) / vss::kFpw)), block(vss::kWave);
-  hipStream_t s = (hipStream_t)stream;
-  switch (mode) {
-    case VSS_MODE_SA: hipLaunchKernelGGL((vss::step_versus_kernel<VSS_MODE_SA>), grid, block, 0, s, args, *vs); break;
-    case VSS_MODE_CMA: hipLaunchKernelGGL((vss::step_versus_kernel<VSS_MODE_CMA>), grid, block, 0, s, args, *vs); break;
-    default: hipLaunchKernelGGL((vss::step_versus_kernel<VSS_MODE_DMA>), grid, block, 0, s, args, *vs); break;
-  }
-  return launch_status();
+  if (int rc = check_step_io(mode, io)) return rc;
+  if (bad(vs->opp_actions, 8) || bad(vs->opp_obs, 16)) return VSS_E_ARG;
+  return launch_step<false, true>(stream, n, mode, p, st, io, nullptr, 0, vs);
 }
 
 int vss_rollout(void* stream, int64_t n, int32_t k_steps, const vss_params* p, const vss_state* st,
