@@ -206,6 +206,45 @@ int vss_step_versus(void* stream, int64_t n_fields, int32_t mode, const vss_para
                     const vss_state* st, const vss_step_io* io, const vss_versus_io* vs);
 
 /*
+ * The yellow team's learner rows of vss_step_mirror (N = n_fields, R = 3 for DMA, else 1); every
+ * member has the shape of the same member of vss_step_io for the mode:
+ *   actions      SA (N,2) yellow robot 0 | CMA (N,6) | DMA (3N,2); 8-B aligned             read
+ *   obs          SA/CMA (N,52) = agent 3 | DMA (3N,52) = agents 3..5; after the reset      write
+ *   terminal_obs same shape, before the reset                                              write
+ *   rew          SA (N,4) = yellow robot 0's | CMA (N,4) = ((r3+r4)+r5)/3 | DMA (3N,4)     write
+ *   reward_sum   (R*N,) = ((goal+grad)+move)+energy of the row, as vss_step                write
+ *   dones        (R*N,) int64 = the field's done, repeated R times                         write
+ *   time_outs    (R*N,) uint8, the same values as io->time_outs                            write
+ *   progress_f   (R*N,) fp32, the same values as io->progress_f                            write
+ * obs, terminal_obs and rew are 16-B aligned, dones 8-B, the float vectors 4-B.
+ */
+typedef struct vss_mirror_io {
+  const float* actions;
+  float* obs;
+  float* terminal_obs;
+  float* rew;
+  float* reward_sum;
+  int64_t* dones;
+  uint8_t* time_outs;
+  float* progress_f;
+} vss_mirror_io;
+
+/*
+ * Two-sided self-play: vss_step in mode SA / CMA / DMA with both teams' robots as learner rows.
+ * `io` is the blue team's and keeps every meaning it has in vss_step for the mode, except that
+ * io->dones_rep is required in all three modes, (R*N,); `yl` is the yellow team's, the same rows
+ * seen from the other side (observations team-relative, goal and grad rewards sign-flipped): every
+ * output equals the FULL step's on the twelve applied actions, agent 0 / 0..2 for blue and agent
+ * 3 / 3..5 for yellow.  Action slots: blue's from io->actions, yellow's from yl->actions (SA 6..7,
+ * CMA / DMA 6..11); in SA blue robots 1-2 and yellow robots 1-2 (slots 2..5, 8..11) keep their OU
+ * update with the values vss_step(SA) would draw (same Philox counter, same operations); CMA and
+ * DMA draw no OU noise.  ou_buf afterwards holds all twelve applied, pre-clamp actions (zeroed for
+ * finished fields); rng_counter advances by 1.  FULL already has both teams' rows: VSS_E_ARG.
+ */
+int vss_step_mirror(void* stream, int64_t n_fields, int32_t mode, const vss_params* params,
+                    const vss_state* st, const vss_step_io* io, const vss_mirror_io* yl);
+
+/*
  * K consecutive FULL-mode steps in one launch for a pre-supplied action sequence (random-action
  * benchmarks, scripted / OU opponents, evaluation): bit-identical to K vss_step(FULL) calls — the
  * same reference semantics per step (envs/vss.py:180-333) — with the field state kept on chip

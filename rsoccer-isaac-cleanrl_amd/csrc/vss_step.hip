@@ -15,11 +15,12 @@
 // Everything is float32 with FMA contraction disabled (-ffp-contract=off and the pragma
 // below): results are bit-identical to the CPU oracle (oracle/vss_oracle.c).
 //
-// The step exists once: step_body<MODE, REPLAY, VERSUS>.  step_kernel<MODE, REPLAY> (vss_step,
-// vss_step_replay) and step_versus_kernel<MODE> (vss_step_versus) are its two __global__ entries;
-// what the versus step does differently sits under `if constexpr (VERSUS)`.  rollout_kernel keeps
-// its own pipelined copy of steps 3-4 and shares the reset (reset_if_done).  On the host,
-// check_step_io and launch_step serve all three step entries.
+// The step exists once: step_body<MODE, REPLAY, VERSUS, MIRROR>.  step_kernel<MODE, REPLAY> (vss_step,
+// vss_step_replay), step_versus_kernel<MODE> (vss_step_versus) and step_mirror_kernel<MODE>
+// (vss_step_mirror) are its three __global__ entries; what the versus and the mirror step do
+// differently sits under `if constexpr (VERSUS)` / `(MIRROR)`.  rollout_kernel keeps its own
+// pipelined copy of steps 3-4 and shares the reset (reset_if_done).  On the host, check_step_io and
+// launch_step serve all four step entries.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
@@ -959,14 +960,31 @@ __device__ __forceinline__ void load_batch(const StepArgs& args, int64_t f0, int
 //     reset has them, and serves two streams: the learner's block and the yellow team's;
 //   * ou_buf afterwards holds all twelve applied, pre-clamp actions.
 // Both observation streams of a wrapped mode are nontemporal, versus or not.
-template <int MODE, bool REPLAY, bool VERSUS>
-__device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus_io& vs) {
+//
+// The mirror step (MIRROR, step_mirror_kernel<MODE>): both teams are learner rows.  The yellow
+// learner's action rows (yl.actions: SA slots 6..7, CMA / DMA 6..11) come in like the versus step's
+// opponent rows, and the yellow team gets every output the blue team gets, each as a second
+// contiguous per-wave stream of the same shape into `yl`, never interleaved with the blue one:
+//   * SA keeps the OU update of blue robots 1-2 and yellow robots 1-2 (slots 2..5, 8..11) exactly as
+//     vss_step(SA) draws it (ou_noise_split<SA>; the pair of slots 6..7 is drawn and overwritten);
+//   * both records carry the mirror slots, the terminal one too: yellow learns, so it needs its
+//     terminal observation (agents 3.. of the table);
+//   * rewards: the yellow agents' terms of rewards_and_done (SA agent 3, CMA ((r3 + r4) + r5) / 3,
+//     DMA agents 3..5), reward_sum, and the field's done / time-out / progress repeated per row;
+//   * io.dones_rep is written in every mode (R rows per field), so that both teams' dones can be
+//     the halves of one tensor.
+template <int MODE, bool REPLAY, bool VERSUS, bool MIRROR = false>
+__device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus_io& vs,
+                                          const vss_mirror_io& yl = vss_mirror_io{}) {
   static_assert(!VERSUS || (!REPLAY && (MODE == VSS_MODE_SA || MODE == VSS_MODE_CMA || MODE == VSS_MODE_DMA)),
                 "versus: wrapped modes only, no replay");
+  static_assert(!MIRROR || (!REPLAY && !VERSUS && (MODE == VSS_MODE_SA || MODE == VSS_MODE_CMA || MODE == VSS_MODE_DMA)),
+                "mirror: wrapped modes only, no replay, not versus");
+  constexpr bool TWO = VERSUS || MIRROR;  // a caller's buffer drives the yellow team
   constexpr int A = MODE == VSS_MODE_FULL ? 6 : (MODE == VSS_MODE_DMA ? 3 : 1);
   constexpr int R = MODE == VSS_MODE_DMA ? 3 : 1;
   constexpr int NL = MODE == VSS_MODE_SA ? 2 : 6;  // learner action floats per field
-  constexpr int REC = VERSUS ? kRecObs6 : obs_rec<A>();  // observation record stride
+  constexpr int REC = TWO ? kRecObs6 : obs_rec<A>();  // observation record stride
   // lanes L and L + 32 hold field L (physics_split); lanes < 32 address the LDS records, so LDS holds
   // 32 plain records or kFpw observation records, whichever is larger
   static_assert(2 * kFpw == kWave, "two lanes per field");
@@ -990,6 +1008,7 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   load_batch<MODE>(args, f0, nv, fl, lane, cur);
   float2 opp[2];  // versus: the wave's (nv, 6) opponent action rows, with the other inputs
   if constexpr (VERSUS) prefetch_lrn<6>(vs.opp_actions + f0 * 6, nv, lane, opp);
+  if constexpr (MIRROR) prefetch_lrn<NL>(yl.actions + f0 * NL, nv, lane, opp);  // the yellow learner's rows
   const int64_t f = f0 + fl;
   const bool valid = fl < nv;
   const bool owner = valid && writer;  // stores the field's outputs
@@ -1013,6 +1032,8 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
     // slots (pairs 0 for SA, 0..2 for CMA/DMA) are overwritten, so their normals are not needed.
     if constexpr (VERSUS) {
       if constexpr (MODE == VSS_MODE_SA) ou_noise_blue_sa(a, k0, k1, (uint32_t)f, ctr);
+    } else if constexpr (MIRROR) {
+      if constexpr (MODE == VSS_MODE_SA) ou_noise_split<MODE>(a, k0, k1, (uint32_t)f, ctr);
     } else if constexpr (REPLAY) {
       // torch.normal(0, 0.15, (N, 2, 3, 2)) of random_ou: the field's 12 recorded samples
       if (valid) {
@@ -1025,12 +1046,17 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
     }
     stage_lrn<NL>(cur.lrn, nv, lds, lane);
     if constexpr (VERSUS) stage_lrn<6>(opp, nv, lds + 6, lane);
+    if constexpr (MIRROR) stage_lrn<NL>(opp, nv, lds + 6, lane);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < NL; ++k) a[k] = rec[k];
     if constexpr (VERSUS) {
 #pragma unroll
       for (int k = 6; k < 12; ++k) a[k] = rec[k];
+    }
+    if constexpr (MIRROR) {
+#pragma unroll
+      for (int k = 6; k < 6 + NL; ++k) a[k] = rec[k];
     }
     __syncthreads();
 #pragma unroll
@@ -1061,9 +1087,10 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   wait_loads();
 
   // -- terminal observation (envs/vss.py:195-196) ----------------------------------------------------------
-  if (lane < kFpw) write_obs_record<A>(orec, b, a);
+  if (lane < kFpw) write_obs_record<MIRROR ? 6 : A>(orec, b, a);
   __syncthreads();
   coop_store_obs<A, 0, REC>(args.io.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL);
+  if constexpr (MIRROR) coop_store_obs<A, 3, REC>(yl.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, true);
   __syncthreads();
 
   // -- reset_dones (envs/vss.py:202, 267-333) ---------------------------------------------------------------
@@ -1072,11 +1099,12 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
                       REPLAY ? args.rd_rounds : (uint32_t)kMaxRejectRounds};
   reset_if_done<REPLAY>(valid, done, rd, b, a, dof);
 
-  // -- observation after reset (envs/vss.py:203); versus: the yellow team's block from the same record -------
-  if (lane < kFpw) write_obs_record<VERSUS ? 6 : A>(orec, b, dof);
+  // -- observation after reset (envs/vss.py:203); versus, mirror: the yellow team's block from the same record
+  if (lane < kFpw) write_obs_record<TWO ? 6 : A>(orec, b, dof);
   __syncthreads();
   coop_store_obs<A, 0, REC>(args.io.obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL || args.nt_obs != 0);
   if constexpr (VERSUS) coop_store_obs<3, 3, REC>(vs.opp_obs + f0 * (52 * 3), nv, lds, tab, lane, true);
+  if constexpr (MIRROR) coop_store_obs<A, 3, REC>(yl.obs + f0 * (52 * A), nv, lds, tab, lane, true);
   __syncthreads();
 
   // -- bookkeeping --------------------------------------------------------------------------------------------
@@ -1092,9 +1120,18 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
       at(args.io.time_outs + f0 * R, (uint32_t)(ufl * R + k)) = time_out;
       at(args.io.progress_f + f0 * R, 4u * (ufl * R + k)) = (float)progress;
     }
-    if constexpr (MODE == VSS_MODE_DMA) {
+    if constexpr (MODE == VSS_MODE_DMA && !MIRROR) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) at(args.io.dones_rep + f0 * 3, 8u * (ufl * 3 + k)) = done;
+    }
+    if constexpr (MIRROR) {
+#pragma unroll
+      for (int k = 0; k < R; ++k) {
+        at(args.io.dones_rep + f0 * R, 8u * (ufl * R + k)) = done;
+        at(yl.dones + f0 * R, 8u * (ufl * R + k)) = done;
+        at(yl.time_outs + f0 * R, (uint32_t)(ufl * R + k)) = time_out;
+        at(yl.progress_f + f0 * R, 4u * (ufl * R + k)) = (float)progress;
+      }
     }
   }
 
@@ -1129,6 +1166,10 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
     if (owner) {
       at(reinterpret_cast<float4*>(args.io.rew) + f0, 16u * (uint32_t)fl) = make_float4(rew[0], rew[1], rew[2], rew[3]);
       at(args.io.reward_sum + f0, 4u * (uint32_t)fl) = ((rew[0] + rew[1]) + rew[2]) + rew[3];
+      if constexpr (MIRROR) {
+        at(reinterpret_cast<float4*>(yl.rew) + f0, 16u * (uint32_t)fl) = make_float4(rew[12], rew[13], rew[14], rew[15]);
+        at(yl.reward_sum + f0, 4u * (uint32_t)fl) = ((rew[12] + rew[13]) + rew[14]) + rew[15];
+      }
     }
   } else if constexpr (MODE == VSS_MODE_CMA) {
     if (owner) {
@@ -1137,6 +1178,13 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
       for (int c = 0; c < 4; ++c) m[c] = ((rew[c] + rew[4 + c]) + rew[8 + c]) / 3.0f;
       at(reinterpret_cast<float4*>(args.io.rew) + f0, 16u * (uint32_t)fl) = make_float4(m[0], m[1], m[2], m[3]);
       at(args.io.reward_sum + f0, 4u * (uint32_t)fl) = ((m[0] + m[1]) + m[2]) + m[3];
+      if constexpr (MIRROR) {
+        float y[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) y[c] = ((rew[12 + c] + rew[16 + c]) + rew[20 + c]) / 3.0f;
+        at(reinterpret_cast<float4*>(yl.rew) + f0, 16u * (uint32_t)fl) = make_float4(y[0], y[1], y[2], y[3]);
+        at(yl.reward_sum + f0, 4u * (uint32_t)fl) = ((y[0] + y[1]) + y[2]) + y[3];
+      }
     }
   } else {
     if (writer) {
@@ -1150,6 +1198,21 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
       for (int ag = 0; ag < 3; ++ag)
         at(args.io.reward_sum + f0 * 3, 4u * ((uint32_t)fl * 3 + ag)) =
             ((rew[4 * ag] + rew[4 * ag + 1]) + rew[4 * ag + 2]) + rew[4 * ag + 3];
+    }
+    if constexpr (MIRROR) {
+      __syncthreads();
+      if (writer) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) rec[k] = rew[12 + k];
+      }
+      __syncthreads();
+      coop_store<12>(yl.rew + f0 * 12, nv, lds, lane);
+      if (owner) {
+#pragma unroll
+        for (int ag = 0; ag < 3; ++ag)
+          at(yl.reward_sum + f0 * 3, 4u * ((uint32_t)fl * 3 + ag)) =
+              ((rew[12 + 4 * ag] + rew[13 + 4 * ag]) + rew[14 + 4 * ag]) + rew[15 + 4 * ag];
+      }
     }
   }
 }
@@ -1166,6 +1229,12 @@ __global__ __launch_bounds__(kWave) void step_kernel(StepArgs args) {
 template <int MODE>
 __global__ __launch_bounds__(kWave) void step_versus_kernel(StepArgs args, vss_versus_io vs) {
   step_body<MODE, false, true>(args, vs);
+}
+
+// The mirror step (vss_step_mirror): both teams are learner rows; `yl` is the yellow team's side.
+template <int MODE>
+__global__ __launch_bounds__(kWave) void step_mirror_kernel(StepArgs args, vss_mirror_io yl) {
+  step_body<MODE, false, false, true>(args, vss_versus_io{}, yl);
 }
 
 // ---- K control steps per launch (open-loop action sequences) -----------------------------------------
@@ -1420,9 +1489,9 @@ static int replay_rounds(const vss_replay_draws* d) {
   return r > vss::kMaxRejectRounds ? -1 : (int)r;
 }
 
-// The vss_step_io checks of vss_step, vss_step_replay and vss_step_versus.  The wrapped modes (the
-// versus step has no other) need ou_buf and reward_sum, DMA needs dones_rep; FULL takes reward_sum
-// if given.
+// The vss_step_io checks of vss_step, vss_step_replay, vss_step_versus and vss_step_mirror.  The
+// wrapped modes (the versus and the mirror step have no other) need ou_buf and reward_sum, DMA needs
+// dones_rep (the mirror step asks for it in every mode itself); FULL takes reward_sum if given.
 static int check_step_io(int32_t mode, const vss_step_io* io) {
   const bool wrapped = mode != VSS_MODE_FULL;
   if (bad(io->actions, wrapped ? 8 : 16) || bad(io->obs, 16) || bad(io->terminal_obs, 16) || bad(io->rew, 16) ||
@@ -1434,11 +1503,12 @@ static int check_step_io(int32_t mode, const vss_step_io* io) {
   return VSS_OK;
 }
 
-// The launch of a checked step: step_versus_kernel<mode> (VERSUS; `vs` given, mode wrapped) or
-// step_kernel<mode, REPLAY>.
-template <bool REPLAY, bool VERSUS>
+// The launch of a checked step: step_versus_kernel<mode> (VERSUS; `vs` given, mode wrapped),
+// step_mirror_kernel<mode> (MIRROR; `yl` given, mode wrapped) or step_kernel<mode, REPLAY>.
+template <bool REPLAY, bool VERSUS, bool MIRROR = false>
 static int launch_step(void* stream, int64_t n, int32_t mode, const vss_params* p, const vss_state* st,
-                       const vss_step_io* io, const vss_replay_draws* rd, int rounds, const vss_versus_io* vs) {
+                       const vss_step_io* io, const vss_replay_draws* rd, int rounds, const vss_versus_io* vs,
+                       const vss_mirror_io* yl = nullptr) {
   if (n == 0) return VSS_OK;
   // FULL: the observation stream nontemporal once the step's footprint (3,101 B per field) is past
   // the 256 MiB Infinity Cache (coop_store_obs)
@@ -1449,11 +1519,12 @@ static int launch_step(void* stream, int64_t n, int32_t mode, const vss_params* 
   auto launch = [&](auto m) {
     constexpr int MODE = decltype(m)::value;
     if constexpr (VERSUS) hipLaunchKernelGGL((vss::step_versus_kernel<MODE>), grid, block, 0, s, args, *vs);
+    else if constexpr (MIRROR) hipLaunchKernelGGL((vss::step_mirror_kernel<MODE>), grid, block, 0, s, args, *yl);
     else hipLaunchKernelGGL((vss::step_kernel<MODE, REPLAY>), grid, block, 0, s, args);
   };
   switch (mode) {
     case VSS_MODE_FULL:
-      if constexpr (!VERSUS) launch(std::integral_constant<int, VSS_MODE_FULL>{});
+      if constexpr (!VERSUS && !MIRROR) launch(std::integral_constant<int, VSS_MODE_FULL>{});
       break;
     case VSS_MODE_SA: launch(std::integral_constant<int, VSS_MODE_SA>{}); break;
     case VSS_MODE_CMA: launch(std::integral_constant<int, VSS_MODE_CMA>{}); break;
@@ -1506,6 +1577,18 @@ int vss_step_versus(void* stream, int64_t n, int32_t mode, const vss_params* p, 
   if (int rc = check_step_io(mode, io)) return rc;
   if (bad(vs->opp_actions, 8) || bad(vs->opp_obs, 16)) return VSS_E_ARG;
   return launch_step<false, true>(stream, n, mode, p, st, io, nullptr, 0, vs);
+}
+
+int vss_step_mirror(void* stream, int64_t n, int32_t mode, const vss_params* p, const vss_state* st,
+                    const vss_step_io* io, const vss_mirror_io* yl) {
+  if (int rc = check_state(n, st)) return rc;
+  if (!p || !io || !yl || mode < VSS_MODE_SA || mode > VSS_MODE_DMA) return VSS_E_ARG;  // FULL has both teams' rows
+  if (int rc = check_step_io(mode, io)) return rc;
+  if (!io->dones_rep) return VSS_E_ARG;  // both teams' dones are rows of the batch, in every mode
+  if (bad(yl->actions, 8) || bad(yl->obs, 16) || bad(yl->terminal_obs, 16) || bad(yl->rew, 16) ||
+      bad(yl->reward_sum, 4) || bad(yl->dones, 8) || bad(yl->time_outs, 1) || bad(yl->progress_f, 4))
+    return VSS_E_ARG;
+  return launch_step<false, false, true>(stream, n, mode, p, st, io, nullptr, 0, nullptr, yl);
 }
 
 int vss_rollout(void* stream, int64_t n, int32_t k_steps, const vss_params* p, const vss_state* st,

@@ -220,6 +220,43 @@ class VSS:
                                       N.ctypes.byref(cio), N.ctypes.byref(vio))
         N.check(rc, "vss_step_versus")
 
+    def native_step_mirror(self, mode: int, actions: torch.Tensor, io: dict, yl: dict) -> None:
+        """native_step in mode SA / CMA / DMA with both teams as learner rows (vss_step_mirror).
+
+        `actions` holds both teams' rows, team-major: (2, rows, width), the blue team's block as
+        native_step takes it, then the yellow team's in the same order.  `io` is the blue team's
+        (as native_step's, with io['dones_rep'] required in every mode) and `yl` the yellow
+        team's: obs, terminal_obs, rew, reward_sum, dones, time_outs, progress_f, each shaped as
+        the same tensor of `io`.  Same buffer checks, one launch, no host sync."""
+        if mode == N.MODE_FULL:
+            raise ValueError("the mirror step is for SA / CMA / DMA; FULL already has both teams' rows")
+        if mode not in (N.MODE_SA, N.MODE_CMA, N.MODE_DMA):
+            raise ValueError(f"unknown mode {mode}")
+        n = self.num_fields
+        rows = 3 * n if mode == N.MODE_DMA else n
+        width = 6 if mode == N.MODE_CMA else 2
+        if actions.numel() != 2 * rows * width:
+            raise ValueError(f"actions must have {2 * rows * width} elements (both teams), got {tuple(actions.shape)}")
+        if actions.dtype != torch.float32 or actions.device != self.device or not actions.is_contiguous():
+            actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        both = actions.view(2, rows * width)
+        _, cio = self._step_io(mode, both[0], io)
+        self._check_buffer("io['dones_rep']", io.get("dones_rep"), rows, torch.long)
+        self._check_buffer("yl['obs']", yl.get("obs"), rows * 52, torch.float32)
+        self._check_buffer("yl['terminal_obs']", yl.get("terminal_obs"), rows * 52, torch.float32)
+        self._check_buffer("yl['rew']", yl.get("rew"), rows * 4, torch.float32)
+        self._check_buffer("yl['reward_sum']", yl.get("reward_sum"), rows, torch.float32)
+        self._check_buffer("yl['dones']", yl.get("dones"), rows, torch.long)
+        self._check_buffer("yl['time_outs']", yl.get("time_outs"), rows, torch.bool)
+        self._check_buffer("yl['progress_f']", yl.get("progress_f"), rows, torch.float32)
+        yio = N.VssMirrorIO(both[1].data_ptr(), yl["obs"].data_ptr(), yl["terminal_obs"].data_ptr(), yl["rew"].data_ptr(),
+                            yl["reward_sum"].data_ptr(), yl["dones"].data_ptr(), yl["time_outs"].data_ptr(),
+                            yl["progress_f"].data_ptr())
+        prm, st = self._c_params(), self._c_state()
+        rc = N.load().vss_step_mirror(N.stream_of(self.device), n, mode, N.ctypes.byref(prm), N.ctypes.byref(st),
+                                      N.ctypes.byref(cio), N.ctypes.byref(yio))
+        N.check(rc, "vss_step_mirror")
+
     def step(self, actions: torch.Tensor):
         """Ext VecTask.step + VSS.pre/post_physics_step for every field (one HIP launch)."""
         self.native_step(N.MODE_FULL, actions, dict(

@@ -41,12 +41,21 @@ def make_env(args):
     """(unwrapped VSS, wrapped env) for args.env_id in {sa, cma, dma} (envs/wrappers.py:21-48).
 
     args.opponent ('ou' when absent) is only validated here: the returned wrapper drives the yellow
-    team with OU noise until its set_opponent(team) is called.  A policy opponent needs the Agent,
+    team with OU noise until its set_opponent(team) is called.  Except 'mirror': the mirror wrapper
+    of the env_id, in which both teams' robots are learner rows and there is no opponent.  A policy opponent needs the Agent,
     which exists only after the env, so the train loop (or any other caller) builds the team --
     vss_amd.opponent.SnapshotOpponent -- and calls set_opponent itself."""
     assert args.cuda
     cfg = default_cfg(args.num_envs)
-    if args.env_id == "dma":
+    opponent = getattr(args, "opponent", "ou")
+    if opponent == "mirror":
+        # both teams' robots are learner rows: num_envs counts rows (dma's precedent), 2 R per field
+        per_field = 6 if args.env_id == "dma" else 2
+        if args.num_envs % per_field != 0:
+            raise ValueError(f"--opponent mirror: --num-envs counts learner rows, {per_field} per field for "
+                             f"{args.env_id}; {args.num_envs} is not a multiple of {per_field}")
+        cfg["env"]["numEnvs"] = args.num_envs // per_field
+    elif args.env_id == "dma":
         assert args.num_envs % 3 == 0
         cfg["env"]["numEnvs"] = int(args.num_envs / 3)
     if getattr(args, "seed", None) is not None:
@@ -56,9 +65,10 @@ def make_env(args):
                headless=not getattr(args, "capture_video", False),
                virtual_screen_capture=getattr(args, "capture_video", False), force_render=False)
     wrappers = {"sa": SingleAgent, "cma": CMA, "dma": DMA}
-    opponent = getattr(args, "opponent", "ou")
-    if opponent != "ou" and not (opponent in ("self", "pool") or os.path.exists(opponent)):
-        raise ValueError(f"--opponent must be ou, self, pool or a checkpoint path, got {opponent!r}")
+    if opponent == "mirror":
+        wrappers = {"sa": MirrorSingleAgent, "cma": MirrorCMA, "dma": MirrorDMA}
+    elif opponent != "ou" and not (opponent in ("self", "pool") or os.path.exists(opponent)):
+        raise ValueError(f"--opponent must be ou, self, pool, mirror or a checkpoint path, got {opponent!r}")
     # the opponent itself (a snapshot of the Agent) is set by the train loop: set_opponent()
     return envs, wrappers[args.env_id](envs)
 
@@ -220,6 +230,99 @@ class DMA(_FusedWrapper):
 
     def __init__(self, env):
         setattr(env, "num_environments", getattr(env, "num_envs", 1) * 3)
+        super().__init__(env)
+        self._action_space = Box(-1.0, 1.0, (env.num_actions,))
+        self._observation_space = Box(-np.inf, np.inf, (env.num_obs,))
+
+
+class _MirrorWrapper(Wrapper):
+    """Two-sided self-play (vss_step_mirror): both teams' robots are learner rows of one step.
+
+    Rows are team-major: rows [0, R N) are exactly the plain wrapper's rows (the blue team's), rows
+    [R N, 2 R N) the yellow team's in the same order, seen from the yellow side (observations
+    team-relative, goal and grad rewards sign-flipped).  Every output is one tensor whose halves
+    the kernel writes as the blue and the yellow block.  SA keeps the OU process for robots 1-2 of
+    both teams; CMA and DMA have no OU robot left."""
+
+    MODE = None
+    FIELD_ROWS = 1      # R: learner rows per field and team
+    ROWS_PER_FIELD = 2  # learner rows per field
+
+    def __init__(self, env: VSS):
+        super().__init__(env)
+        setattr(env, "num_environments", env.num_fields * self.ROWS_PER_FIELD)
+        self.action_buf = env.dof_velocity_buf.clone()  # (N,2,3,2): the twelve applied actions (SA: OU state)
+        dev = env.device
+        rows = env.num_fields * self.ROWS_PER_FIELD
+        self._obs = torch.zeros((rows, env.num_obs), device=dev)
+        self._terminal_obs = torch.zeros_like(self._obs)
+        self._rews = torch.zeros((rows, 4), device=dev)
+        self._reward = torch.zeros(rows, device=dev)
+        self._time_outs = torch.zeros(rows, dtype=torch.bool, device=dev)
+        self._progress = torch.zeros(rows, device=dev)
+        self._dones = torch.zeros(rows, dtype=torch.long, device=dev)
+        # the halves of each output: the blue team's block (vss_step_io) and the yellow team's (vss_mirror_io)
+        h = rows // 2
+        blue, yellow = (lambda t: t[:h]), (lambda t: t[h:])
+        self._io = dict(ou_buf=self.action_buf, obs=blue(self._obs), terminal_obs=blue(self._terminal_obs),
+                        rew=blue(self._rews), reward_sum=blue(self._reward), dones_rep=blue(self._dones),
+                        time_outs=blue(self._time_outs), progress_f=blue(self._progress))
+        self._yl = dict(obs=yellow(self._obs), terminal_obs=yellow(self._terminal_obs), rew=yellow(self._rews),
+                        reward_sum=yellow(self._reward), dones=yellow(self._dones), time_outs=yellow(self._time_outs),
+                        progress_f=yellow(self._progress))
+        self._first_obs()
+
+    def _first_obs(self):
+        env, R = self.env, self.FIELD_ROWS
+        full = torch.empty((env.num_fields, 2, 3, env.num_obs), device=env.device)
+        env.compute_observations(full, n_agents=6)
+        self._obs.view(2, env.num_fields, R, env.num_obs).copy_(full[:, :, :R].transpose(0, 1))
+        return {"obs": self._obs}
+
+    def set_opponent(self, team=None):
+        raise ValueError("a mirror wrapper has no opponent: both teams are the learner's rows")
+
+    def reset(self, **kwargs):
+        self.env.reset(**kwargs)
+        return self._first_obs()
+
+    def step(self, action):
+        self.env.native_step_mirror(self.MODE, action, self._io, self._yl)
+        infos = {"rews": self._rews, "terminal_observation": self._terminal_obs, "time_outs": self._time_outs,
+                 "progress_buffer": self._progress}
+        return {"obs": self._obs}, self._reward, self._dones, infos
+
+
+class MirrorSingleAgent(_MirrorWrapper):
+    """Learners = blue robot 0 and yellow robot 0; the other four robots follow OU noise."""
+
+    MODE = N.MODE_SA
+
+    def __init__(self, env):
+        super().__init__(env)
+        self._action_space = Box(-1.0, 1.0, (env.num_actions,))
+        self._observation_space = Box(-np.inf, np.inf, (env.num_obs,))
+
+
+class MirrorCMA(_MirrorWrapper):
+    """Centralised multi-agent on both sides: one 6-vector per team and field."""
+
+    MODE = N.MODE_CMA
+
+    def __init__(self, env):
+        super().__init__(env)
+        self._action_space = Box(-1.0, 1.0, (env.num_actions * 3,))
+        self._observation_space = Box(-np.inf, np.inf, (env.num_obs,))
+
+
+class MirrorDMA(_MirrorWrapper):
+    """Decentralised multi-agent on both sides: each of the six robots is one learner row."""
+
+    MODE = N.MODE_DMA
+    FIELD_ROWS = 3
+    ROWS_PER_FIELD = 6
+
+    def __init__(self, env):
         super().__init__(env)
         self._action_space = Box(-1.0, 1.0, (env.num_actions,))
         self._observation_space = Box(-np.inf, np.inf, (env.num_obs,))

@@ -23,7 +23,10 @@ the loop -- and the machinery under it lives in vss_amd/:
 * logging is optional (TensorBoard if installed, else a CSV of the same scalars; no W&B);
 * `--opponent self|pool|PATH` (a build addition): the yellow team is a policy -- a snapshot of the learner, refreshed
   every `--opponent-update-every` updates, a league of past snapshots (OpponentPool), or a checkpoint -- instead
-  of OU noise (vss_amd/opponent.py).
+  of OU noise (vss_amd/opponent.py);
+* `--opponent mirror` (a build addition): two-sided self-play -- the current policy plays both teams and both
+  teams' transitions are rows of the PPO batch (envs/wrappers.py Mirror*, vss_step_mirror); `--num-envs` counts
+  learner rows, two per field (dma: six).
 """
 from __future__ import annotations
 
@@ -122,7 +125,9 @@ def parse_args(argv=None):
                    help="the yellow team: 'ou' (Ornstein-Uhlenbeck noise, the reference's wrappers), 'self' (a frozen "
                         "snapshot of the learner's actor, vss_amd.opponent.SnapshotOpponent, inside the fused step), "
                         "'pool' (a league of past snapshots, vss_amd.opponent.OpponentPool) or the path of an agent "
-                        "checkpoint in the reference's format (a fixed opponent)")
+                        "checkpoint in the reference's format (a fixed opponent); 'mirror': two-sided self-play, the "
+                        "learner plays both teams and both teams' rows are trained on (--num-envs counts rows: two "
+                        "per field, six for dma)")
     p.add_argument("--opponent-update-every", type=int, default=1,
                    help="--opponent self: copy the learner's weights into the snapshot after every K-th update "
                         "(0: keep the initial weights); --opponent pool: add a snapshot to the pool every K-th update")
@@ -412,6 +417,10 @@ def train(args, on_update=None):
             counter = opponent.counter
             opponent(torch.zeros_like(fused_env._opp_act), fused_env._opp_obs)
             opponent.counter = counter
+    elif opponent_mode == "mirror":
+        # two-sided self-play: both teams' robots are learner rows of the wrapper (vss_step_mirror); no snapshot,
+        # no sync, no opponent forward -- storage, the fused policy, GAE and the update only see more rows
+        pass
     elif opponent_mode != "ou":
         from vss_amd.opponent import KIND_OF_ENV, SnapshotOpponent
         opponent = SnapshotOpponent(agent, KIND_OF_ENV[args.env_id], seed=seed * 7919 + 104729)
@@ -530,6 +539,9 @@ def train(args, on_update=None):
                "update_s": t_upd, "opponent_version": opponent.version if opponent is not None else -1,
                "episodes": float(ep_cnt.sum()), "mean_return": float(ep_ret.sum() / ep_cnt.sum().clamp(min=1)),
                **{k: float(v) for k, v in stats.items()}}
+        if opponent_mode == "mirror":  # rows are team-major: the halves of the per-row sums the loop keeps
+            for team, half in (("blue", slice(0, E // 2)), ("yellow", slice(E // 2, E))):
+                rec[f"mean_return_{team}"] = float(ep_ret[half].sum() / ep_cnt[half].sum().clamp(min=1))
         history.append(rec)
         every = getattr(args, "opponent_update_every", 1)
         if opponent_mode == "pool":

@@ -50,6 +50,7 @@ STATE_CHANNELS = 58
 CH_BALL_X, CH_BALL_Y, CH_BALL_VX, CH_BALL_VY = 0, 1, 2, 3
 CH_RX, CH_RY, CH_RQX, CH_RQY, CH_RQZ, CH_RQW, CH_RVX, CH_RVY, CH_RW = 4, 10, 16, 22, 28, 34, 40, 46, 52
 EXPORTED = ("vss_abi_version", "vss_source_hash", "vss_error_string", "vss_step", "vss_step_replay", "vss_step_versus",
+            "vss_step_mirror",
             "vss_actor_forward", "vss_actor_forward_grouped", "vss_policy_sample_grouped", "vss_match_tally",
             "vss_rollout", "vss_reset_dones",
             "vss_reset_dones_replay",
@@ -93,6 +94,12 @@ class VssStepIO(ctypes.Structure):
 class VssVersusIO(ctypes.Structure):
     """The yellow team's side of vss_step_versus (include/vss.h vss_versus_io)."""
     _fields_ = [(k, ctypes.c_void_p) for k in ("opp_actions", "opp_obs")]
+
+
+class VssMirrorIO(ctypes.Structure):
+    """The yellow team's learner rows of vss_step_mirror (include/vss.h vss_mirror_io)."""
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ("actions", "obs", "terminal_obs", "rew", "reward_sum", "dones", "time_outs", "progress_f")]
 
 
 MAX_ACTOR_GROUPS = 16
@@ -167,6 +174,8 @@ def load() -> ctypes.CDLL:
     L.vss_step_replay.restype = ctypes.c_int
     L.vss_step_versus.argtypes = [P, i64, i32, P, P, P, P]
     L.vss_step_versus.restype = ctypes.c_int
+    L.vss_step_mirror.argtypes = [P, i64, i32, P, P, P, P]
+    L.vss_step_mirror.restype = ctypes.c_int
     L.vss_reset_dones_replay.argtypes = [P, i64, P, P, P]
     L.vss_reset_dones_replay.restype = ctypes.c_int
     L.vss_rollout.argtypes = [P, i64, i32, P, P, P]
