@@ -615,12 +615,17 @@ int vss_adv_part_sum(void* stream, int32_t nparts, const double* part, double* o
  * Adam -- with two launches, and the split GEMMs' torch.sum reductions with one launch per backward.
  *
  * vss_grad_sq_partials: partial[b] = sum of grad[i]^2 over block b's chunk, b < count =
- *   vss_grad_sq_partials_count(n) (<= 1024; -1 for n <= 0); fixed order (deterministic).
+ *   vss_grad_sq_partials_count(n) (= min(1024, ceil(n / 4096)); -1 for n <= 0): with chunk =
+ *   ceil(n / count), block b's chunk is the elements [b chunk, (b + 1) chunk) below n (a block whose
+ *   range starts at or past n writes 0); fixed order (deterministic).
  * vss_adam_step_clipped: norm = sqrt(sum of the nparts partials); with max_norm >= 0 the gradients are
  *   scaled in place by min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_: max_norm 0 zeroes them, as
  *   torch's does), with max_norm < 0 they are left alone (no clip requested); then Adam's step `step`
- *   (>= 1, the count after this step) with torch's fused-Adam arithmetic: m = b1 m + (1 - b1) g,
- *   v = b2 v + (1 - b2) g^2, p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps).
+ *   (>= 1, the count after this step): m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2,
+ *   p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps), evaluated in fp32 from these fp32
+ *   hyper-parameters (1 - powf(b, step)).  Torch's Adam forms the bias corrections in double from double
+ *   betas; against that, 1 - b2^step is up to 1.3e-5 relative away at small step counts and about half of
+ *   it reaches the update (measured figures: DESIGN.md §5.7; pinned by tests/test_optim.py).
  *   norm_out (1 float, may be NULL) receives the pre-clip norm.  All buffers n fp32 elements.
  * vss_sum_parts: `count` (1..32) jobs; job q: dst[r * dst_ld + c] = sum over s = 0 .. parts - 1 of
  *   src[s * part_stride + r * src_ld + c], r < rows, c < cols, in a fixed order (parts s = w + 4 (u + 8 i)

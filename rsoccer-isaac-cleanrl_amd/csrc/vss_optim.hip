@@ -7,11 +7,16 @@
 // instead of torch's per-tensor norm chain + multi-tensor Adam (~8 launches, ~130 us per minibatch at the
 // reference's 4,095 envs, profiles/r05_ppo_4095_minibatch_window.txt):
 //
-//   vss_grad_sq_partials:  partial[b] = sum of g^2 over block b's chunk (fixed order: deterministic)
+//   vss_grad_sq_partials:  partial[b] = sum of g^2 over block b's chunk, the elements [b chunk, (b + 1) chunk)
+//                          below n with chunk = ceil(n / count) (fixed order: deterministic)
 //   vss_adam_step_clipped: every block sums the partials (same fixed order), norm = sqrt, the clip
 //                          coefficient min(1, max_norm / (norm + 1e-6)) of clip_grad_norm_, g *= coef
-//                          (written back, as clip_grad_norm_ leaves the gradients), then Adam's update
-//                          with torch's fused-Adam arithmetic (bias corrections from the step count).
+//                          (written back, as clip_grad_norm_ leaves the gradients), then Adam's update:
+//                          the header's formula evaluated in fp32 from the fp32 hyper-parameters, the bias
+//                          corrections as 1 - powf(beta, step).  Torch forms them in double from double
+//                          betas: 1 - b2^t is then up to 1.3e-5 relative away at small t (fp32's 0.999
+//                          alone moves it by t |b2f - b2| b2^(t-1) / (1 - b2^t)), about half of which
+//                          reaches the update (measured: DESIGN.md §5.7, tests/test_optim.py).
 //
 // And the split GEMMs' partial sums (weight gradients over row parts, bias-gradient column sums) are
 // reduced for a whole MLP backward in ONE launch (vss_sum_parts: a list of jobs, each dst[r][c] = the sum
@@ -81,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void adam_step_kernel(int64_t n, int32_t 
     coef = c < 1.f ? c : 1.f;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
-  // torch's fused Adam (opmath fp32): bias corrections from the step count
+  // bias corrections from the step count, in fp32 (torch's are formed in double: see the header comment)
   const float bc1 = 1.f - powf(beta1, step), bc2 = 1.f - powf(beta2, step);
   const float step_size = lr / bc1, bc2_sqrt = sqrtf(bc2);
   const int64_t stride = (int64_t)gridDim.x * kThreads;

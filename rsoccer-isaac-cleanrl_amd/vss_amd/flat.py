@@ -99,9 +99,12 @@ class FlatAdam(torch.optim.Optimizer):
     parameter and gradient buffers: one launch (vss_adam_step_clipped) per step, which also applies the
     clip_grad_norm_ (ppo…:353) requested through FlatGrads.clip_norm_ just before -- instead of torch's
     norm chain and multi-tensor Adam (~8 launches, ~130 us per minibatch at the reference's 4,095 envs).
-    Same update rule, in torch's fused-Adam arithmetic (tests/test_ppo.py); param_groups[0]["lr"] is read
-    at every step, so --anneal-lr / --adaptative-lr act on it as on torch's Adam.  A clip to max_norm 0
-    zeroes the gradients, as clip_grad_norm_'s does; a step without a clip request does not clip."""
+    Same update rule, evaluated in fp32 from the fp32-rounded hyper-parameters (bias corrections as
+    1 - powf(beta, step); torch forms them in double from double betas, which at small step counts moves
+    the update by up to ~8e-6 of lr: measured in tests/test_optim.py, figures in DESIGN.md §5.7);
+    param_groups[0]["lr"] is read at every step, so --anneal-lr / --adaptative-lr act on it as on torch's
+    Adam.  A clip to max_norm 0 zeroes the gradients, as clip_grad_norm_'s does; a step without a clip request
+    does not clip."""
 
     NO_CLIP = -1.0  # vss_adam_step_clipped's "no clip requested" (max_norm < 0)
 
