@@ -609,6 +609,36 @@ int vss_minibatch_gather(void* stream, int64_t mb, int64_t rows_pad, int64_t bat
 int vss_adv_part_sum(void* stream, int32_t nparts, const double* part, double* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * A rollout's advantages and returns in one launch (csrc/vss_returns.hip): the train loop's
+ * timeout-aware GAE (ppo_continuous_action_isaacgym.py compute_gae; the reference's ppo…:282-296),
+ * bit for bit.  T = n_steps, E = n_rows (the batch's learner rows).  rewards, values, next_dones,
+ * next_timeouts, advantages, returns and next_values / term_values are (T, E) fp32, row-major
+ * [t * E + e]; v_last is (E,); every pointer 4-B aligned.  next_dones and next_timeouts are the loop's
+ * float storage: nonzero means set.
+ *   Form A (next_values given; term_values and v_last NULL): nv[t][e] = next_values[t][e], as
+ *     compute_gae takes it.
+ *   Form B (next_values NULL; term_values and v_last given): the merge of vss_amd/policy.py
+ *     TerminalValues.next_values in the kernel,
+ *       nv[t][e] = next_dones[t][e] != 0 ? term_values[t][e] : (t + 1 < T ? values[t + 1][e] : v_last[e])
+ *     -- a select, not arithmetic: term_values of rows that did not reset are never read into a sum.
+ * Exactly one form must be present.  Per column e, walking t = T-1 .. 0 from last = 0, in float32 with
+ * the operation order of the torch expressions and no FMA contraction:
+ *   nnt   = (next_dones != 0 && next_timeouts == 0) ? 0.f : 1.f
+ *   delta = ((rewards + (gamma * nv) * nnt) - values)
+ *   last  = delta + ((gamma_lambda * (1.f - next_dones)) * last)
+ *   advantages[t][e] = last;  returns[t][e] = last + values[t][e]
+ * gamma_lambda = (float)((double)gamma * (double)lambda): the product is formed in double and rounded
+ * once, as Python's `gamma * lam` reaches torch; (float)gamma * (float)lambda is another number for
+ * some settings (0.997, 0.9).  advantages and returns must not overlap any input (nor each other).
+ * VSS_E_ARG, before any HIP call: a null required pointer, both forms or neither, one of term_values /
+ * v_last without the other, a pointer that is not 4-B aligned, negative n_steps or n_rows, a non-finite
+ * gamma or gamma_lambda.  n_steps == 0 or n_rows == 0: VSS_OK, no launch.
+ * ------------------------------------------------------------------------------------------- */
+int vss_gae(void* stream, int64_t n_steps, int64_t n_rows, const float* rewards, const float* values,
+            const float* next_values, const float* term_values, const float* v_last, const float* next_dones,
+            const float* next_timeouts, float gamma, float gamma_lambda, float* advantages, float* returns);
+
+/* ---------------------------------------------------------------------------------------------
  * The update's gradient bookkeeping on flat buffers (csrc/vss_optim.hip; vss_amd/flat.py
  * FlatGrads / FlatAdam).  Replaces, per minibatch, nn.utils.clip_grad_norm_ (ppo…:353)
  * and optim.Adam(eps=1e-5).step() (ppo…:166,354) -- torch's per-tensor norm chain and multi-tensor

@@ -47,7 +47,7 @@ from torch.distributions.normal import Normal
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from envs._gym import Box, ObservationWrapper  # noqa: E402
-from vss_amd import minibatch as MB  # noqa: E402
+from vss_amd import minibatch as MB, returns as RET  # noqa: E402
 from vss_amd.flat import FlatAdam, FlatGrads  # noqa: E402,F401
 from vss_amd.minibatch import (DirectRows, EpochPermutations, autocast, direct_minibatch,  # noqa: E402,F401
                                direct_minibatch_ok, disable_graph_packet_capture, make_minibatch_graph,
@@ -454,6 +454,10 @@ def train(args, on_update=None):
     values = torch.zeros((T, E), device=device)
     next_values = torch.zeros((T, E), device=device)
     term = TerminalValues(T, E, obs_dim, device) if fused is not None else None
+    # advantages and returns: on the GPU one vss_gae launch per update into these buffers (vss_amd/returns.py);
+    # VSS_GAE=torch keeps compute_gae and the torch merge of the terminal values -- the same bits
+    gae_kernel = RET.kernel_selected(device)
+    advantages, returns = torch.zeros((2, T, E), device=device) if gae_kernel else (None, None)
     graph = make_minibatch_graph(agent, flat, args, T * E, obs_dim, act_dim, device)
 
     # outside the clock, as the reference's env and Agent construction before ppo…:244: the kernels' first
@@ -510,7 +514,9 @@ def train(args, on_update=None):
             ep_cnt.add_(d)
             if step <= 2:
                 ep_first[step] = first_done_stats(d, info)
-        if term is not None:
+        if term is not None and gae_kernel:
+            term_values, v_last = term.terminal_values(fused, next_obs)
+        elif term is not None:
             next_values = term.next_values(fused, values, next_dones, next_obs)
         if device.type == "cuda":
             torch.cuda.synchronize()
@@ -523,9 +529,13 @@ def train(args, on_update=None):
                         writer.add_scalar(f"rws/episodic_{k}", v, gs)
                     writer.add_scalar("rws/episodic_length", row[6], gs)
 
-        with torch.no_grad():
-            advantages, returns = compute_gae(rewards, values, next_values, next_dones, next_timeouts,
-                                              args.gamma, args.gae_lambda)
+        if gae_kernel:  # with the fused policy the terminal values are merged in the kernel (form B)
+            form = dict(term_values=term_values, v_last=v_last) if term is not None else dict(next_values=next_values)
+            RET.gae(rewards, values, next_dones, next_timeouts, args.gamma, args.gae_lambda, out=(advantages, returns), **form)
+        else:
+            with torch.no_grad():
+                advantages, returns = compute_gae(rewards, values, next_values, next_dones, next_timeouts,
+                                                  args.gamma, args.gae_lambda)
         t_upd = time.time()
         stats = ppo_update(agent, optimizer, flat, args, obs.reshape((-1,) + obs_dim), logprobs.reshape(-1),
                            actions.reshape((-1,) + act_dim), advantages.reshape(-1), returns.reshape(-1),

@@ -270,11 +270,14 @@ class TerminalValues:
         self.term_obs[step].copy_(terminal_obs.reshape(self.term_obs.shape[1:]))
         self.term_mask[step].copy_(done)
 
-    def next_values(self, fused, values, next_dones, next_obs):
-        """(T, E) next_values: the masked terminal pass where a field reset, else values[t + 1].  When
-        the rollout's values come from the GEMM chain (FusedPolicy.chain_active), the reset rows are
+    def terminal_values(self, fused, next_obs):
+        """The critic passes after the rollout, unmerged: (term_values, v_last).  term_values (T, E) holds
+        critic(terminal_obs) in the rows that reset -- the other rows keep whatever an earlier rollout left
+        there and must not be read -- and v_last (E,) = critic(next_obs), the value above the last step.
+        vss_amd.returns.gae takes the pair (form B) and selects between them and values[t + 1] in its kernel.
+        When the rollout's values come from the GEMM chain (FusedPolicy.chain_active), the reset rows are
         gathered and evaluated by the same chain (one host sync for their count, once per rollout), so
-        next_values stays exactly critic(terminal_obs) of one evaluator."""
+        term_values stays exactly critic(terminal_obs) of one evaluator."""
         if fused.chain_active(self.E):
             idx = self.term_mask.view(-1).nonzero().squeeze(1)
             tv = self.term_values.view(-1)
@@ -283,5 +286,10 @@ class TerminalValues:
                                .view(-1))
         else:
             fused.get_value_masked(self.term_obs, self.term_mask, self.term_values.view(self.T * self.E, 1))
-        v_last = fused.get_value(next_obs).view(1, self.E)
-        return torch.where(next_dones.bool(), self.term_values, torch.cat([values[1:], v_last], 0))
+        return self.term_values, fused.get_value(next_obs).view(self.E)
+
+    def next_values(self, fused, values, next_dones, next_obs):
+        """(T, E) next_values for compute_gae (the torch path): terminal_values' masked terminal pass where a
+        field reset, else values[t + 1]."""
+        term_values, v_last = self.terminal_values(fused, next_obs)
+        return torch.where(next_dones.bool(), term_values, torch.cat([values[1:], v_last.view(1, self.E)], 0))
