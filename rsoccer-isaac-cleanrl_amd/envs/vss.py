@@ -136,6 +136,28 @@ class VSS:
         return N.VssState(self.state.data_ptr(), self.progress_buf.data_ptr(), self.reset_buf.data_ptr(),
                           self.dof_velocity_buf.data_ptr(), self.rng_counter.data_ptr())
 
+    # ------------------------------------------------------------------------------ checkpoint
+    def _state_tensors(self) -> dict:
+        return {k: getattr(self, k) for k in ("state", "progress_buf", "reset_buf", "dof_velocity_buf", "rng_counter",
+                                              "timeout_buf", "progress_f_buf", "obs_buf", "terminal_obs_buf", "rew_buf")}
+
+    def state_dict(self) -> dict:
+        """Everything a later step depends on, on the CPU (vss_amd.checkpoint): the SoA state, the progress,
+        reset, velocity and Philox-counter buffers, the persistent output buffers and the four runtime reward
+        weights.  The Philox key (`seed`) is the configuration's."""
+        from vss_amd.checkpoint import to_cpu
+        return to_cpu({**self._state_tensors(),
+                       "rew_weights": [float(self.w_goal), float(self.w_grad), float(self.w_move), float(self.w_energy)]})
+
+    def load_state_dict(self, state: dict) -> None:
+        """Copy a state_dict() into the existing buffers (the reference-compatible views stay views of them)."""
+        from vss_amd.checkpoint import copy_entries, entry
+        copy_entries("VSS", self._state_tensors(), state)
+        weights = entry(state, "rew_weights", "VSS")
+        if len(weights) != 4:
+            raise ValueError(f"VSS.rew_weights: expected 4 weights, got {weights}")
+        self.w_goal, self.w_grad, self.w_move, self.w_energy = (float(w) for w in weights)
+
     # ------------------------------------------------------------------------------ spaces
     @property
     def num_envs(self):

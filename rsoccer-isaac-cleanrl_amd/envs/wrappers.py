@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from vss_amd import _native as N
+from vss_amd.checkpoint import copy_entries, to_cpu
 
 from ._gym import Box, Wrapper
 from .vss import VSS, default_cfg
@@ -94,6 +95,19 @@ class RecordEpisodeStatisticsTorch(Wrapper):
         self.returned_return_sum = torch.zeros(n, dtype=torch.float32, device=self.device)
         return observations
 
+    def _state_tensors(self) -> dict:
+        if self.episode_returns is None:
+            raise ValueError("RecordEpisodeStatisticsTorch: reset() allocates the statistics; call it first")
+        return {k: getattr(self, k) for k in ("episode_returns", "episode_lengths", "returned_episode_returns",
+                                              "returned_episode_lengths", "returned_return_sum")}
+
+    def state_dict(self) -> dict:
+        """The five running-statistics tensors on the CPU (vss_amd.checkpoint)."""
+        return to_cpu(self._state_tensors())
+
+    def load_state_dict(self, state: dict) -> None:
+        copy_entries("RecordEpisodeStatisticsTorch", self._state_tensors(), state)
+
     def step(self, action):
         observations, rewards, dones, infos = super().step(action)
         rews = infos["rews"]
@@ -171,6 +185,21 @@ class _FusedWrapper(Wrapper):
         if self._opponent is not None:
             self._first_opp_obs()
         return self._first_obs()
+
+    def _state_tensors(self) -> dict:
+        own = self.ROWS_PER_FIELD != 1  # else time_outs / progress are the env's buffers, saved with the env
+        return dict(action_buf=self.action_buf, obs=self._obs, terminal_obs=self._terminal_obs, rews=self._rews,
+                    reward=self._reward, dones=self._dones, time_outs=self._time_outs if own else None,
+                    progress=self._progress if own else None, opp_obs=self._opp_obs, opp_act=self._opp_act)
+
+    def state_dict(self) -> dict:
+        """The wrapper's own buffers on the CPU (vss_amd.checkpoint): the OU state, the learner's current
+        observations (the next rollout's first input) and the other outputs, the opponent's rows when one is
+        set.  The env's and the opponent's state are saved by their owners."""
+        return to_cpu({k: t for k, t in self._state_tensors().items() if t is not None})
+
+    def load_state_dict(self, state: dict) -> None:
+        copy_entries(type(self).__name__, self._state_tensors(), state)
 
     def _rews_view(self):
         return self._rews
@@ -281,6 +310,17 @@ class _MirrorWrapper(Wrapper):
 
     def set_opponent(self, team=None):
         raise ValueError("a mirror wrapper has no opponent: both teams are the learner's rows")
+
+    def _state_tensors(self) -> dict:
+        return dict(action_buf=self.action_buf, obs=self._obs, terminal_obs=self._terminal_obs, rews=self._rews,
+                    reward=self._reward, dones=self._dones, time_outs=self._time_outs, progress=self._progress)
+
+    def state_dict(self) -> dict:
+        """The full-row tensors on the CPU (vss_amd.checkpoint); the `_io` / `_yl` halves are views of them."""
+        return to_cpu(self._state_tensors())
+
+    def load_state_dict(self, state: dict) -> None:
+        copy_entries(type(self).__name__, self._state_tensors(), state)
 
     def reset(self, **kwargs):
         self.env.reset(**kwargs)

@@ -47,7 +47,7 @@ from torch.distributions.normal import Normal
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from envs._gym import Box, ObservationWrapper  # noqa: E402
-from vss_amd import minibatch as MB, returns as RET  # noqa: E402
+from vss_amd import checkpoint as CK, minibatch as MB, returns as RET  # noqa: E402
 from vss_amd.flat import FlatAdam, FlatGrads  # noqa: E402,F401
 from vss_amd.minibatch import (DirectRows, EpochPermutations, autocast, direct_minibatch,  # noqa: E402,F401
                                direct_minibatch_ok, disable_graph_packet_capture, make_minibatch_graph,
@@ -138,6 +138,8 @@ def parse_args(argv=None):
                    help="--opponent pool: the share of the slots that plays the newest snapshot")
     p.add_argument("--opponent-pfsp-power", type=float, default=1.0,
                    help="--opponent pool: the other slots draw a snapshot with probability ~ (1 - win rate) ** power")
+    p.add_argument("--checkpoint-every", type=int, default=0, help="every K-th update: <run>-state.pt, <run>-agent-u<update>.pt")
+    p.add_argument("--resume", type=str, default=None, help="a <run>-state.pt: go on after its update, bit-equal (DESIGN.md §15)")
     args = p.parse_args(argv)
     args.batch_size = int(args.num_envs * args.num_steps)
     args.minibatch_size = int(args.batch_size // args.num_minibatches)
@@ -364,9 +366,10 @@ def train(args, on_update=None):
     with that update's history record -- may return True to stop training early (tools/time_to_score.py
     evaluates the live policy there)."""
     disable_graph_packet_capture()  # effective only while nothing has initialised the GPU yet
+    saved = CK.begin(args)  # --checkpoint-every / --resume: refusals and the state file, before any GPU work
     world, rank, local = setup_distributed()
     run_name = f"{args.exp_name}_ppo-{args.env_id}_{args.seed}"
-    writer = make_writer(args, run_name, rank)
+    writer = make_writer(args, run_name, rank, append=saved is not None)
     writer.add_text("hyperparameters", "|param|value|\n|-|-|\n%s" % "\n".join(f"|{k}|{v}|" for k, v in vars(args).items()))
 
     seed = args.seed + rank
@@ -470,12 +473,14 @@ def train(args, on_update=None):
         graph.prepare(obs.reshape((-1,) + obs_dim), actions.reshape((-1,) + act_dim), logprobs.reshape(-1),
                       values.reshape(-1), values.reshape(-1), values.reshape(-1), world)
     args.graph_prepare_s = time.perf_counter() - t_prep
-    global_step = 0
     start_time = time.time()
     next_obs = envs.reset()
     num_updates = args.num_updates if args.num_updates is not None else args.total_timesteps // (args.batch_size * world)
-    history = []
-    for update in range(1, num_updates + 1):
+    # update 1, step 0, no history, this clock -- or with --resume the saved ones: after the warm-up and graph.prepare the
+    # saved state replaces the fresh one (next_obs is the wrapper's observation buffer, filled by the copy)
+    owners = CK.owners(optimizer, unwrapped_env, fused_env, envs, fused, opponent)
+    first_update, global_step, history, start_time = CK.resume(saved, agent, owners, gen, device, start_time)
+    for update in range(first_update, num_updates + 1):
         if args.anneal_lr:
             optimizer.param_groups[0]["lr"] = annealed_lr(update, num_updates, args.learning_rate)
         t_roll = time.time()
@@ -561,6 +566,8 @@ def train(args, on_update=None):
             rec["opponent_pool_winrate"] = opponent.end_update(agent, update, every)["winrate"]
         if opponent is not None and opponent_mode == "self" and every > 0 and update % every == 0:
             opponent.sync(agent, version=update)
+        # --checkpoint-every: the state update + 1 starts from (rec["checkpoint_s"]; part of wall_s and sps)
+        sps = CK.checkpoint(args, rank, run_name, rec, agent, owners, gen, device, history, start_time)
         for k, name in (("v_loss", "value_loss"), ("pg_loss", "policy_loss"), ("entropy", "entropy"),
                         ("old_approx_kl", "old_approx_kl"), ("approx_kl", "approx_kl"), ("clipfrac", "clipfrac")):
             writer.add_scalar(f"losses/{name}", rec[k], global_step)

@@ -1,0 +1,280 @@
+"""The training state file of `--checkpoint-every` / `--resume` (ppo_continuous_action_isaacgym.py).
+
+One `torch.save` dict of CPU tensors and plain Python values (it loads with `weights_only=True`), written
+atomically: a temporary file in the same directory, flush + fsync, then `os.replace`, so a kill during the
+write leaves the previous state file as it was.  Each owner of state -- VSS, the fused and mirror wrappers,
+RecordEpisodeStatisticsTorch, FusedPolicy, SnapshotOpponent, OpponentPool, FlatAdam -- has a `state_dict()` /
+`load_state_dict()` pair built on `to_cpu` and `copy_into` below; the train loop puts them together.
+
+    save_state(path, state)                      # adds FORMAT_VERSION and the library's source hash
+    state = load_state(path)                     # refuses another FORMAT_VERSION
+    check_compatible(state["args"], args)        # ValueError on a structural difference
+"""
+from __future__ import annotations
+
+import os
+import random
+import time
+
+import numpy as np
+import torch
+
+FORMAT_VERSION = 1
+
+# what the saved buffers' shapes, the Philox keys and the set of state owners are built from: these must
+# equal the saved ones (the seed too: the env's Philox key and the policies' seeds are rebuilt from it)
+STRUCTURAL = ("env_id", "num_envs", "num_steps", "seed", "opponent", "opponent_pool_slots", "opponent_pool_size",
+              "fused_policy", "amp", "cuda")
+# set by train() itself or about the checkpoint, not hyper-parameters: never reported as changed
+_NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
+
+
+def opponent_mode(value) -> str:
+    """--opponent as a structural value: ou / self / pool / mirror, or 'checkpoint' for any path."""
+    value = "ou" if value is None else str(value)
+    return value if value in ("ou", "self", "pool", "mirror") else "checkpoint"
+
+
+def plain_args(args) -> dict:
+    """vars(args) restricted to what a weights_only load takes back: None, bool, int, float and str."""
+    d = args if isinstance(args, dict) else vars(args)
+    return {k: v for k, v in d.items() if v is None or isinstance(v, (bool, int, float, str))}
+
+
+def check_compatible(saved_args, args, log=print) -> list:
+    """Compare a state file's args with this command line's.  A structural argument that differs raises a
+    ValueError naming the key and both values; every other argument is taken from `args`, and each one that
+    differs from the saved value is reported once through `log` (None: silent).  Returns the changed keys."""
+    saved, new = plain_args(saved_args), plain_args(args)
+    for k in STRUCTURAL:
+        a, b = saved.get(k), new.get(k)
+        if k == "opponent":
+            a, b = opponent_mode(a), opponent_mode(b)
+        if a != b:
+            raise ValueError(f"--resume: {k} is structural and differs: the state file has {a!r}, this command line {b!r}")
+    changed = []
+    for k in sorted(set(saved) | set(new)):
+        if k in _NOT_COMPARED:  # (a structural key that differs here: another path of a checkpoint opponent)
+            continue
+        a, b = saved.get(k), new.get(k)
+        if a != b and not (isinstance(a, float) and isinstance(b, float) and a != a and b != b):
+            changed.append(k)
+            if log is not None:
+                log(f"--resume: {k} changed from {a!r} (saved) to {b!r}; the new value is used")
+    return changed
+
+
+def source_hash() -> str:
+    from . import _native
+    return _native.source_hash()
+
+
+def _write(obj, f) -> None:
+    torch.save(obj, f)
+
+
+def atomic_save(path: str, obj) -> int:
+    """torch.save(obj) to `path` through a temporary file in the same directory: flush + fsync, then
+    os.replace.  A failure or a kill on the way leaves `path` as it was.  Returns the file's size in bytes."""
+    path = os.path.abspath(path)
+    folder = os.path.dirname(path)
+    os.makedirs(folder, exist_ok=True)
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        with open(tmp, "wb") as f:
+            _write(obj, f)
+            f.flush()
+            os.fsync(f.fileno())
+        size = os.path.getsize(tmp)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    fd = os.open(folder, os.O_RDONLY)  # the rename itself
+    try:
+        os.fsync(fd)
+    finally:
+        os.close(fd)
+    return size
+
+
+def save_state(path: str, state: dict) -> int:
+    """Write `state` (+ format_version, source_hash) to `path` atomically; returns the file's size in bytes."""
+    return atomic_save(path, dict(state, format_version=FORMAT_VERSION,
+                                  source_hash=state.get("source_hash") or source_hash()))
+
+
+def load_state(path: str) -> dict:
+    """The state dict of `path` on the CPU; a file of another FORMAT_VERSION (or none) is refused."""
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    version = state.get("format_version") if isinstance(state, dict) else None
+    if version != FORMAT_VERSION:
+        raise ValueError(f"{path}: state format version {version!r}, this build reads version {FORMAT_VERSION}")
+    return state
+
+
+# ---- building blocks of the owners' state_dict() / load_state_dict() -----------------------------------------
+def to_cpu(tree):
+    """A copy of a tree of dicts / lists / tuples with every tensor detached onto the CPU."""
+    if isinstance(tree, torch.Tensor):
+        return tree.detach().to("cpu", copy=True)
+    if isinstance(tree, dict):
+        return {k: to_cpu(v) for k, v in tree.items()}
+    if isinstance(tree, (list, tuple)):
+        return [to_cpu(v) for v in tree]
+    return tree
+
+
+def copy_into(dst: torch.Tensor, src, name: str) -> None:
+    """dst.copy_(src) after checking shape and dtype: the existing tensor, and every view of it, stays."""
+    if not isinstance(src, torch.Tensor):
+        raise ValueError(f"{name}: expected a tensor, got {type(src).__name__}")
+    if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+        raise ValueError(f"{name}: saved {tuple(src.shape)} {src.dtype} does not fit {tuple(dst.shape)} {dst.dtype}")
+    with torch.no_grad():
+        dst.copy_(src)
+
+
+def entry(state: dict, key: str, owner: str):
+    if not isinstance(state, dict) or key not in state:
+        raise ValueError(f"{owner}: the saved state has no entry {key!r}")
+    return state[key]
+
+
+def copy_entries(owner: str, tensors: dict, state: dict) -> None:
+    """copy_into for every named tensor of an owner (None: the owner does not have it, nothing is read)."""
+    for k, dst in tensors.items():
+        if dst is not None:
+            copy_into(dst, entry(state, k, owner), f"{owner}.{k}")
+
+
+def python_rng_state(state=None) -> list:
+    """random.getstate() (or the given one) as nested lists."""
+    version, internal, gauss = random.getstate() if state is None else state
+    return [version, list(internal), gauss]
+
+
+def python_rng_tuple(saved) -> tuple:
+    version, internal, gauss = saved
+    return (int(version), tuple(int(v) for v in internal), gauss)
+
+
+def numpy_rng_state() -> list:
+    name, keys, pos, has_gauss, cached = np.random.get_state()
+    return [str(name), torch.from_numpy(keys.astype(np.int64)), int(pos), int(has_gauss), float(cached)]
+
+
+def numpy_rng_tuple(saved) -> tuple:
+    name, keys, pos, has_gauss, cached = saved
+    return (str(name), np.asarray(keys, dtype=np.int64).astype(np.uint32), int(pos), int(has_gauss), float(cached))
+
+
+def rng_state(gen: torch.Generator, device) -> dict:
+    """Every generator the loop or the code under it may draw from: reading a state consumes nothing."""
+    device = torch.device(device)
+    return {"gen": gen.get_state().clone(), "python": python_rng_state(), "numpy": numpy_rng_state(),
+            "torch_cpu": torch.get_rng_state().clone(),
+            "torch_device": torch.cuda.get_rng_state(device).clone() if device.type == "cuda" else None}
+
+
+def load_rng_state(saved: dict, gen: torch.Generator, device) -> None:
+    device = torch.device(device)
+    gen.set_state(entry(saved, "gen", "rng"))
+    random.setstate(python_rng_tuple(entry(saved, "python", "rng")))
+    np.random.set_state(numpy_rng_tuple(entry(saved, "numpy", "rng")))
+    torch.set_rng_state(entry(saved, "torch_cpu", "rng"))
+    if device.type == "cuda" and saved.get("torch_device") is not None:
+        torch.cuda.set_rng_state(saved["torch_device"], device)
+
+
+# ---- the train loop's side (ppo_continuous_action_isaacgym.py train) ---------------------------------------------
+def checkpoint_paths(args, run_name: str, update: int | None = None):
+    """(the state file, the agent file of `update`) of --checkpoint-every, both in the run's directory."""
+    folder = f"{args.save_path}/{run_name}"
+    return f"{folder}/{run_name}-state.pt", None if update is None else f"{folder}/{run_name}-agent-u{update:06d}.pt"
+
+
+def begin(args):
+    """Before any GPU work or process group: refuse what is not built, and with --resume read the state file
+    and compare its command line with this one.  Returns the saved state, or None without --resume."""
+    every, path = int(getattr(args, "checkpoint_every", 0) or 0), getattr(args, "resume", None)
+    if every < 0:
+        raise ValueError(f"--checkpoint-every must be >= 0, got {every}")
+    if (every or path) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("--checkpoint-every / --resume with WORLD_SIZE > 1: per-rank state files are not built "
+                         "(the env state, the Philox counters and a league's tallies are per rank); run them on one rank")
+    if not path:
+        return None
+    saved = load_state(path)
+    check_compatible(entry(saved, "args", "state"), args)
+    if saved.get("source_hash") != source_hash():
+        print(f"--resume: {path} was written by a library built from other sources ({saved.get('source_hash')}, here "
+              f"{source_hash()}): a bit-equal continuation is no longer promised", flush=True)
+    if getattr(args, "log", False):
+        print(f"--resume: {path}, update {saved['update']}, step {saved['global_step']}", flush=True)
+    return saved
+
+
+def owners(optimizer, env, wrapper, episode_stats, fused=None, opponent=None) -> dict:
+    """What carries state from one update to the next, each with a state_dict() / load_state_dict() pair."""
+    out = {"optimizer": optimizer, "env": env, "wrapper": wrapper, "episode_stats": episode_stats}
+    if fused is not None:
+        out["fused_policy"] = fused
+    if opponent is not None:
+        out["opponent"] = opponent
+    return out
+
+
+def training_state(args, agent, owners: dict, gen, device, update: int, global_step: int, wall_s: float,
+                   history: list) -> dict:
+    """Everything the next update depends on, as CPU tensors and plain values: the agent's
+    parameters, each owner's state_dict(), every generator's state and the loop's scalars.  Reading it draws no
+    random number and rebinds no buffer."""
+    return {"args": plain_args(args), "agent": to_cpu(dict(agent.state_dict())),
+            "owners": {k: o.state_dict() for k, o in owners.items()}, "rng": rng_state(gen, device),
+            "update": int(update), "global_step": int(global_step), "wall_s": float(wall_s),
+            "history": [dict(r) for r in history]}
+
+
+def load_training_state(state: dict, agent, owners: dict, gen, device) -> None:
+    """Put a training_state() back: every tensor is copied into the one that exists (the agent's parameters stay
+    views of the flat buffer), the generators last."""
+    copy_entries("agent", dict(agent.state_dict()), entry(state, "agent", "state"))
+    saved = entry(state, "owners", "state")
+    if sorted(saved) != sorted(owners):
+        raise ValueError(f"--resume: the state file holds {sorted(saved)}, this run has {sorted(owners)}")
+    for k, o in owners.items():
+        o.load_state_dict(saved[k])
+    load_rng_state(entry(state, "rng", "state"), gen, device)
+
+
+def resume(saved, agent, owners: dict, gen, device, start_time: float):
+    """(first update, global_step, history, start_time) of the loop: 1, 0, [] and the given clock without a
+    saved state; else the state is loaded and the loop goes on after the saved update, on the saved clock
+    (wall_s and sps include the time before the interruption)."""
+    if saved is None:
+        return 1, 0, [], start_time
+    load_training_state(saved, agent, owners, gen, device)
+    return (int(saved["update"]) + 1, int(saved["global_step"]), [dict(r) for r in saved["history"]],
+            time.time() - float(saved["wall_s"]))
+
+
+def checkpoint(args, rank: int, run_name: str, rec: dict, agent, owners: dict, gen, device, history: list,
+               start_time: float) -> int:
+    """The end of an update's bookkeeping: on every --checkpoint-every-th update rank 0 writes the state file and
+    the agent file.  Sets rec["checkpoint_s"] (0.0 when nothing was written) and, after a write, rec["wall_s"] and
+    rec["sps"], which include it; returns rec["sps"].  The state file's own copy of this record keeps
+    checkpoint_s 0.0 and the clock from before the write."""
+    rec["checkpoint_s"] = 0.0
+    every, update = int(getattr(args, "checkpoint_every", 0) or 0), rec["update"]
+    if every and update % every == 0 and rank == 0:
+        t0 = time.time()
+        state_path, agent_path = checkpoint_paths(args, run_name, update)
+        save_state(state_path, training_state(args, agent, owners, gen, device, update, rec["global_step"], rec["wall_s"],
+                                              history))
+        atomic_save(agent_path, agent.state_dict())  # the reference's format: play.py, --opponent PATH
+        rec["checkpoint_s"] = time.time() - t0
+        rec["wall_s"] = time.time() - start_time
+        rec["sps"] = int(rec["global_step"] / rec["wall_s"])
+    return rec["sps"]

@@ -123,6 +123,20 @@ class FlatAdam(torch.optim.Optimizer):
         self.norm = torch.zeros(1, device=flat.flat.device)
         self._max_norm = self.NO_CLIP
 
+    def state_dict(self) -> dict:
+        """The moments, the step count and the learning rate (vss_amd.checkpoint; not torch's layout: the
+        moments are the two flat buffers).  The parameters are the FlatGrads' and are saved by its owner."""
+        from .checkpoint import to_cpu
+        return to_cpu({"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "steps": int(self.steps),
+                       "lr": float(self.param_groups[0]["lr"])})
+
+    def load_state_dict(self, state: dict) -> None:
+        """Copy a state_dict() into the existing buffers (shape and dtype checked, ValueError names the entry)."""
+        from .checkpoint import copy_entries, entry
+        copy_entries("FlatAdam", {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq}, state)
+        self.steps = int(entry(state, "steps", "FlatAdam"))
+        self.param_groups[0]["lr"] = float(entry(state, "lr", "FlatAdam"))
+
     def zero_grad(self, set_to_none: bool = True):
         """Zero the flat gradient buffer (the .grad tensors are views of it and stay in place)."""
         self.flat.zero()

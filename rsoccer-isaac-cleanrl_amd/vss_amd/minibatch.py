@@ -547,6 +547,7 @@ def warmup_kernels(args, train) -> float:
     w.num_envs = 3 * 16384 if args.env_id == "dma" else 16384
     w.num_steps, w.num_updates, w.total_timesteps = 8, 1, 0
     w.log, w.evaluate, w.capture_video, w.track, w.kernel_warmup = False, False, False, False, False
+    w.checkpoint_every, w.resume = 0, None  # the throwaway run neither writes a state file nor loads one
     w.batch_size = int(w.num_envs * w.num_steps)
     w.minibatch_size = int(w.batch_size // w.num_minibatches)
     train(w)

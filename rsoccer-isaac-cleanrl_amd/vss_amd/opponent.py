@@ -26,6 +26,7 @@ import torch
 
 from . import _native as N
 from . import policy as _policy
+from .checkpoint import copy_entries, copy_into, entry, python_rng_state, python_rng_tuple, to_cpu
 from .policy import FusedPolicy
 
 KINDS = {"x3": 2, "cma": 6}  # kind -> the policy's action width
@@ -95,6 +96,17 @@ class SnapshotOpponent:
         if version is not None:
             self.version = int(version)
         return self
+
+    def state_dict(self) -> dict:
+        """The frozen actor's weights, their label and the policy's Philox counter (vss_amd.checkpoint)."""
+        return {"actor": to_cpu(dict(self.actor.state_dict())), "version": int(self.version),
+                "policy": self.policy.state_dict()}
+
+    def load_state_dict(self, state: dict) -> None:
+        copy_entries("SnapshotOpponent.actor", dict(self.actor.state_dict()), entry(state, "actor", "SnapshotOpponent"))
+        self.policy.refresh()
+        self.version = int(entry(state, "version", "SnapshotOpponent"))
+        self.policy.load_state_dict(entry(state, "policy", "SnapshotOpponent"))
 
     @torch.no_grad()
     def __call__(self, act, obs):
@@ -225,6 +237,44 @@ class OpponentPool:
             g.logstd[i] = s.logstd.data_ptr()
         self._groups = g
         return self.versions
+
+    def state_dict(self) -> dict:
+        """The whole league (vss_amd.checkpoint): every snapshot's actor weights (log-std among them), label and
+        totals in order, the snapshot of each slot as an index into that list, the Philox counter, the host
+        generator's state and the device tally.  Taken at an update boundary, after end_update() has dealt the
+        slots, every slot holds a member of the list."""
+        if any(s not in self.snapshots for s in self.slot_snapshots):
+            raise ValueError("OpponentPool.state_dict: a slot holds an evicted snapshot; call it after assign()")
+        return {"snapshots": [{"actor": to_cpu(dict(s.actor.state_dict())), "version": int(s.version),
+                               "totals": [int(v) for v in s.totals]} for s in self.snapshots],
+                "slots": [self.snapshots.index(s) for s in self.slot_snapshots],
+                "counter": int(self.counter), "rng": python_rng_state(self.rng.getstate()), "tally": to_cpu(self.tally)}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Rebuild the league from a state_dict(): the snapshots on storage of this pool's own, the slots put
+        back through hold(), so the kernel's group table points at the live packed weights."""
+        saved = entry(state, "snapshots", "OpponentPool")
+        slots = [int(i) for i in entry(state, "slots", "OpponentPool")]
+        if not 1 <= len(saved) <= self.capacity:
+            raise ValueError(f"OpponentPool.snapshots: {len(saved)} saved snapshots, this pool keeps 1 to {self.capacity}")
+        if len(slots) != self.count or any(not 0 <= i < len(saved) for i in slots):
+            raise ValueError(f"OpponentPool.slots: {slots} does not deal {self.count} slots among {len(saved)} snapshots")
+        copy_into(self.tally, entry(state, "tally", "OpponentPool"), "OpponentPool.tally")
+        snapshots = []
+        for i, sv in enumerate(saved):
+            s = self.snapshots[i] if i < len(self.snapshots) else _Snapshot(self.snapshots[0].actor, 0)
+            copy_entries(f"OpponentPool.snapshots[{i}].actor", dict(s.actor.state_dict()), entry(sv, "actor", "snapshot"))
+            s.policy.refresh()
+            s.version = int(entry(sv, "version", "snapshot"))
+            totals = [int(v) for v in entry(sv, "totals", "snapshot")]
+            if len(totals) != 4:
+                raise ValueError(f"OpponentPool.snapshots[{i}].totals: expected 4 counts, got {totals}")
+            s.totals = totals
+            snapshots.append(s)
+        self.snapshots = snapshots
+        self.hold([snapshots[i] for i in slots])
+        self.counter = int(entry(state, "counter", "OpponentPool"))
+        self.rng.setstate(python_rng_tuple(entry(state, "rng", "OpponentPool")))
 
     def check_env(self, env):
         """Win and loss are read from the sign of the goal reward: that needs a positive goal weight."""

@@ -52,6 +52,18 @@ class FusedPolicy:
         self._keep = {}
         self.refresh()
 
+    def state_dict(self) -> dict:
+        """The Philox call counter (vss_amd.checkpoint).  The seed is the constructor's; the packed weights and
+        the bf16 planes follow the agent's parameters through refresh()."""
+        return {"counter": int(self.counter)}
+
+    def load_state_dict(self, state: dict) -> None:
+        from .checkpoint import entry
+        counter = entry(state, "counter", "FusedPolicy")
+        if isinstance(counter, bool) or not isinstance(counter, int) or counter < 0:
+            raise ValueError(f"FusedPolicy.counter: expected a non-negative int, got {counter!r}")
+        self.counter = counter
+
     @staticmethod
     def _linears(seq):
         return [m for m in seq if isinstance(m, torch.nn.Linear)]
