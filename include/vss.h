@@ -697,6 +697,27 @@ int vss_episode_stats(void* stream, int64_t rows, const float* rews, const int64
 int vss_match_tally(void* stream, int64_t n_fields, int32_t rows_per_field, int64_t group_fields, int32_t count,
                     const float* rew, const int64_t* dones, const float* progress_f, int64_t* tally);
 
+/* ---------------------------------------------------------------------------------------------
+ * The scripted benchmark team (csrc/vss_scripted.hip; vss_amd/scripted.py): the six
+ * wheel commands of one team per field from robot 0's observation row, in one launch.  A pure
+ * function of that row -- no state, no random draw, graph-safe -- and equal bit for bit to
+ * vss_amd.scripted.reference_actions, which specifies controller `version` operation by operation.
+ * VSS_SCRIPTED_VERSION names the controller: a change of behaviour gets a new number, 1 stays.
+ *
+ * obs: robot 0's 52-float row of field 0 for the team driven (team frame: it attacks +x); field f's row is
+ *   at obs + f * obs_field_stride floats.  Only the ball's position and the own robots' positions and
+ *   headings are read (floats 0..27 of the row); rows of robots 1-2 are not read.  obs_field_stride: a
+ *   multiple of 4, >= 52 -- 156 for a contiguous (N,3,52) team block, 312 for one team of (N,2,3,52).
+ * act: field f's six floats (robots 0..2: left, right wheel, each in [-1, 1]) at act + f * act_field_stride;
+ *   act_field_stride: a multiple of 2, >= 6 -- 6 for (N,3,2), 12 for one team's half of (N,2,3,2).
+ *   Nothing else is written: the gap between two fields' six floats is untouched.
+ * VSS_E_ARG, before any HIP call: a null pointer, obs not 16-B or act not 8-B aligned, a stride below its
+ * minimum or not a multiple as above, version != 1, n_fields < 0.  n_fields == 0: VSS_OK, no launch.
+ * ------------------------------------------------------------------------------------------- */
+#define VSS_SCRIPTED_VERSION 1
+int vss_scripted_team(void* stream, int64_t n_fields, int32_t version, const float* obs, int64_t obs_field_stride,
+                      float* act, int64_t act_field_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,8 +68,8 @@ def make_env(args):
     wrappers = {"sa": SingleAgent, "cma": CMA, "dma": DMA}
     if opponent == "mirror":
         wrappers = {"sa": MirrorSingleAgent, "cma": MirrorCMA, "dma": MirrorDMA}
-    elif opponent != "ou" and not (opponent in ("self", "pool") or os.path.exists(opponent)):
-        raise ValueError(f"--opponent must be ou, self, pool, mirror or a checkpoint path, got {opponent!r}")
+    elif opponent != "ou" and not (opponent in ("self", "pool", "scripted") or os.path.exists(opponent)):
+        raise ValueError(f"--opponent must be ou, self, pool, mirror, scripted or a checkpoint path, got {opponent!r}")
     # the opponent itself (a snapshot of the Agent) is set by the train loop: set_opponent()
     return envs, wrappers[args.env_id](envs)
 

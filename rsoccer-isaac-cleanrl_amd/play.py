@@ -8,7 +8,8 @@ tallies stay on the device, and the host finds the exact step at which the refer
 stopped, counting nothing after it.
 
 Teams (play.py:26-102): 'zero', 'ou', and checkpoints of 'ppo-sa' / 'ppo-sa-x3' / 'ppo-cma' /
-'ppo-dma' agents.  Checkpoints are loaded with `torch.load(weights_only=True)`.  The reference's
+'ppo-dma' agents, and 'scripted' (a build addition: the deterministic benchmark team of
+vss_amd/scripted.py, one HIP launch per step).  Checkpoints are loaded with `torch.load(weights_only=True)`.  The reference's
 BASELINE_TEAMS point at base_nets/*.pt files that are not part of the reference snapshot
 (.MISSING_LARGE_BLOBS); `baseline_teams()` returns whichever of them exist plus zero/ou.
 """
@@ -24,6 +25,7 @@ import torch
 from envs._gym import Box
 from envs.wrappers import random_ou
 from ppo_continuous_action_isaacgym import Agent
+from vss_amd import scripted as _scripted
 
 COUNT_FIELDS = 1065  # play.py:158 counts dones among the first 1065 fields (test.py:35)
 
@@ -45,6 +47,26 @@ class TeamZero(Team):
 class TeamOU(Team):
     def __call__(self, act, obs):
         act.copy_(random_ou(act))
+
+
+class TeamScripted(Team):
+    """The scripted benchmark team: attacker, defender and keeper from robot 0's row, one vss_scripted_team
+    launch per call (vss_amd/scripted.py; not among the reference's teams).  It keeps no state and draws no random
+    number; `version` names the controller and is all its state dict holds."""
+
+    version = _scripted.VERSION
+
+    def __call__(self, act, obs):
+        _scripted.scripted_actions(act, obs, self.version)
+
+    def state_dict(self) -> dict:
+        return {"version": int(self.version)}
+
+    def load_state_dict(self, state: dict) -> None:
+        saved = state.get("version") if isinstance(state, dict) else None
+        if saved != self.version:
+            raise ValueError(f"TeamScripted: the saved state is of controller version {saved!r}, this build plays "
+                             f"version {self.version}")
 
 
 class TeamAgent(Team):
@@ -91,6 +113,8 @@ def get_team(algo, path=None, device="cuda:0"):
         return TeamZero()
     if algo == "ou":
         return TeamOU()
+    if algo == "scripted":
+        return TeamScripted()
     raise ValueError(f"Unknown algo: {algo}")
 
 

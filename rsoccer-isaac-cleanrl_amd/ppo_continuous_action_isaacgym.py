@@ -26,7 +26,11 @@ the loop -- and the machinery under it lives in vss_amd/:
   of OU noise (vss_amd/opponent.py);
 * `--opponent mirror` (a build addition): two-sided self-play -- the current policy plays both teams and both
   teams' transitions are rows of the PPO batch (envs/wrappers.py Mirror*, vss_step_mirror); `--num-envs` counts
-  learner rows, two per field (dma: six).
+  learner rows, two per field (dma: six);
+* `--opponent scripted` (a build addition): the yellow team is the scripted benchmark team (vss_amd/scripted.py,
+  one vss_scripted_team launch per step) -- a fixed opponent that plays, with nothing to snapshot or sync;
+* `--eval-every K` (a build addition): every K-th update rank 0 plays the live agent against fixed teams on a
+  separate arena env (vss_amd/arena.py) and adds the scores to the update's record; the training's bits do not move.
 """
 from __future__ import annotations
 
@@ -125,9 +129,15 @@ def parse_args(argv=None):
                    help="the yellow team: 'ou' (Ornstein-Uhlenbeck noise, the reference's wrappers), 'self' (a frozen "
                         "snapshot of the learner's actor, vss_amd.opponent.SnapshotOpponent, inside the fused step), "
                         "'pool' (a league of past snapshots, vss_amd.opponent.OpponentPool) or the path of an agent "
-                        "checkpoint in the reference's format (a fixed opponent); 'mirror': two-sided self-play, the "
+                        "checkpoint in the reference's format (a fixed opponent); 'scripted': the deterministic scripted "
+                        "benchmark team (vss_amd/scripted.py); 'mirror': two-sided self-play, the "
                         "learner plays both teams and both teams' rows are trained on (--num-envs counts rows: two "
                         "per field, six for dma)")
+    p.add_argument("--eval-every", type=int, default=0,
+                   help="every K-th update rank 0 plays the live agent against --eval-teams on a separate arena env and "
+                        "adds rec['eval'] / rec['eval_s'] (vss_amd/arena.py); 0: off, the loop is as without the flag")
+    p.add_argument("--eval-fields", type=int, default=1024, help="--eval-every: fields (= counted episodes per team)")
+    p.add_argument("--eval-teams", type=str, default="zero,ou,scripted", help="--eval-every: yellow teams, comma separated")
     p.add_argument("--opponent-update-every", type=int, default=1,
                    help="--opponent self: copy the learner's weights into the snapshot after every K-th update "
                         "(0: keep the initial weights); --opponent pool: add a snapshot to the pool every K-th update")
@@ -331,7 +341,9 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
     as the blue team against every baseline team available (play.py: zero, OU and the
     base_nets checkpoints present), `args.eval_matches` matches each; for SA also as 'sa-x3'
     (the single-agent policy controlling all three blue robots).  Scores go to the writer under
-    the reference's Validation/* names and are returned."""
+    the reference's Validation/* names and are returned.  The scripted team (a build addition) is played and
+    reported too, as Validation/Score/scripted and Validation/Length/scripted, outside Score Mean / Length
+    Mean: those stay over the reference's teams."""
     from play import baseline_teams, get_team, play_matches
     unwrapped_env.w_goal, unwrapped_env.w_grad, unwrapped_env.w_move, unwrapped_env.w_energy = 1.0, 0.0, 0.0, 0.0
     device = unwrapped_env.device
@@ -354,6 +366,8 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
             res[f"Validation/Length/{team}"] = t_len / len(seeds)
         res["Validation/Score Mean"] = sum(scores) / len(scores)
         res["Validation/Length Mean"] = sum(lengths) / len(lengths)
+        res["Validation/Score/scripted"], res["Validation/Length/scripted"] = play_matches(
+            unwrapped_env, blue, get_team("scripted"), args.eval_matches)
         for k, v in res.items():
             writer.add_scalar(f"{algo}/{k}", v, global_step)
         print(f"evaluation {algo}: " + ", ".join(f"{k} {v:.3f}" for k, v in res.items()), flush=True)
@@ -400,43 +414,13 @@ def train(args, on_update=None):
     if args.fused_policy and device.type == "cuda" and args.amp == "none":
         from vss_amd.policy import FusedPolicy, TerminalValues
         fused = FusedPolicy(agent, seed=seed * 7919 + 17)
-    # --opponent self | PATH: the yellow team is a frozen copy of this Agent's actor (or a checkpoint's) inside
-    # the fused step, with a Philox stream of its own; 'ou' leaves the wrapper on the kernel's OU process.
-    # The weights are the same on every rank, so sync() is a local copy (no collective).
-    opponent = None
+    # --opponent self | pool | scripted | PATH: the yellow team is a policy inside the fused step (a frozen copy of this
+    # Agent's actor, a league of past snapshots, the scripted benchmark team or a checkpoint's actor), built and set on
+    # the wrapper by vss_amd.opponent.make_opponent; 'ou' leaves the wrapper on the kernel's OU process, and 'mirror' has
+    # no opponent: both teams' robots are learner rows.  Weights are equal on every rank: no collective anywhere.
+    from vss_amd.opponent import make_opponent
     opponent_mode = getattr(args, "opponent", "ou")
-    # 'pool': a league of past snapshots (OpponentPool), each on its slice of this rank's fields; the weights are
-    # equal on every rank, the match tallies -- and so the assignments -- are per rank (no collective either).
-    if opponent_mode == "pool":
-        from vss_amd.opponent import KIND_OF_ENV, OpponentPool
-        opponent = OpponentPool(agent, KIND_OF_ENV[args.env_id], unwrapped_env.num_fields,
-                                slots=getattr(args, "opponent_pool_slots", 8),
-                                capacity=getattr(args, "opponent_pool_size", 16),
-                                latest=getattr(args, "opponent_pool_latest", 0.5),
-                                pfsp_power=getattr(args, "opponent_pfsp_power", 1.0), seed=seed * 7919 + 104729)
-        fused_env.set_opponent(opponent)
-        if getattr(args, "kernel_warmup", False):
-            # outside the clock: the pool's forward at this run's row count; the Philox counter is put back
-            counter = opponent.counter
-            opponent(torch.zeros_like(fused_env._opp_act), fused_env._opp_obs)
-            opponent.counter = counter
-    elif opponent_mode == "mirror":
-        # two-sided self-play: both teams' robots are learner rows of the wrapper (vss_step_mirror); no snapshot,
-        # no sync, no opponent forward -- storage, the fused policy, GAE and the update only see more rows
-        pass
-    elif opponent_mode != "ou":
-        from vss_amd.opponent import KIND_OF_ENV, SnapshotOpponent
-        opponent = SnapshotOpponent(agent, KIND_OF_ENV[args.env_id], seed=seed * 7919 + 104729)
-        if opponent_mode != "self":
-            opponent.load(opponent_mode)
-        fused_env.set_opponent(opponent)
-        if getattr(args, "kernel_warmup", False):
-            # outside the clock, like warmup_kernels below: the opponent's forward at this run's own row count
-            # (under 16,384 opponent rows it is the actor-only fused kernel, which the 16,384-env warm-up run
-            # does not reach); the Philox counter is put back, so the training's draws do not change
-            counter = opponent.policy.counter
-            opponent(torch.zeros_like(fused_env._opp_act), fused_env._opp_obs)
-            opponent.policy.counter = counter
+    opponent = make_opponent(args, agent, fused_env, unwrapped_env.num_fields, seed * 7919 + 104729)
     # torch's Adam (ppo…:166) -- on the GPU FlatAdam: the same update rule over the flat parameter and
     # gradient buffers, with the gradient clip, in one launch per minibatch (vss_adam_step_clipped)
     if device.type == "cuda":
@@ -479,6 +463,11 @@ def train(args, on_update=None):
     # update 1, step 0, no history, this clock -- or with --resume the saved ones: after the warm-up and graph.prepare the
     # saved state replaces the fresh one (next_obs is the wrapper's observation buffer, filled by the copy)
     owners = CK.owners(optimizer, unwrapped_env, fused_env, envs, fused, opponent)
+    # --eval-every: rank 0's arena, a second env and FusedPolicy of its own; it owns nothing a checkpoint carries
+    arena = None
+    if int(getattr(args, "eval_every", 0) or 0) > 0 and rank == 0:
+        from vss_amd.arena import Arena
+        arena = Arena(args, agent, device)
     first_update, global_step, history, start_time = CK.resume(saved, agent, owners, gen, device, start_time)
     for update in range(first_update, num_updates + 1):
         if args.anneal_lr:
@@ -566,6 +555,10 @@ def train(args, on_update=None):
             rec["opponent_pool_winrate"] = opponent.end_update(agent, update, every)["winrate"]
         if opponent is not None and opponent_mode == "self" and every > 0 and update % every == 0:
             opponent.sync(agent, version=update)
+        if arena is not None and update % args.eval_every == 0:
+            # after the opponent bookkeeping, before the checkpoint write: rec["eval"], rec["eval_s"]; wall_s and sps
+            # include it (as checkpoint_s), rollout_s and update_s do not
+            arena.evaluate_into(rec, update, writer, start_time)
         # --checkpoint-every: the state update + 1 starts from (rec["checkpoint_s"]; part of wall_s and sps)
         sps = CK.checkpoint(args, rank, run_name, rec, agent, owners, gen, device, history, start_time)
         for k, name in (("v_loss", "value_loss"), ("pg_loss", "policy_loss"), ("entropy", "entropy"),

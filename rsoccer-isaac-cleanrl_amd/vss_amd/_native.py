@@ -41,7 +41,8 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "vss.h"
 STAMPED = (os.path.join(CSRC, "vss_step.hip"), os.path.join(CSRC, "vss_update.hip"),
            os.path.join(CSRC, "vss_policy.hip"), os.path.join(CSRC, "vss_gemm_x6.hip"),
            os.path.join(CSRC, "vss_loss.hip"), os.path.join(CSRC, "vss_optim.hip"),
-           os.path.join(CSRC, "vss_returns.hip"), os.path.join(CSRC, "vss_loss_row.h"), HEADER,
+           os.path.join(CSRC, "vss_returns.hip"), os.path.join(CSRC, "vss_scripted.hip"),
+           os.path.join(CSRC, "vss_loss_row.h"), HEADER,
            os.path.join(CSRC, "Makefile"))
 
 ABI_VERSION = 2
@@ -66,7 +67,7 @@ EXPORTED = ("vss_abi_version", "vss_source_hash", "vss_error_string", "vss_step"
             "vss_ppo_loss_direct", "vss_minibatch_gather_parts", "vss_minibatch_gather", "vss_adv_part_sum",
             "vss_first_layer_bf16x6", "vss_linear_tanh_loss_blocks_bf16x6", "vss_linear_tanh_loss_bf16x6",
             "vss_ppo_loss_fused_finish", "vss_randperm_scratch_bytes", "vss_randperm", "vss_randperm_bits",
-            "vss_gae")
+            "vss_gae", "vss_scripted_team")
 
 
 class VssParams(ctypes.Structure):
@@ -284,6 +285,8 @@ def load() -> ctypes.CDLL:
     L.vss_randperm_bits.restype = ctypes.c_int
     L.vss_gae.argtypes = [P, i64, i64] + [P] * 7 + [f32, f32, P, P]
     L.vss_gae.restype = ctypes.c_int
+    L.vss_scripted_team.argtypes = [P, i64, i32, P, i64, P, i64]
+    L.vss_scripted_team.restype = ctypes.c_int
     if L.vss_abi_version() != ABI_VERSION:
         raise NativeError(f"libvss_amd ABI {L.vss_abi_version()} != expected {ABI_VERSION}")
     _lib = L

@@ -1,0 +1,118 @@
+"""`--eval-every K`: the live agent against fixed yellow teams during training.
+
+Every K-th update rank 0 plays the agent as it is on a second, separate env of `--eval-fields` fields, wrapped
+as the run's own `--env-id` (SA / CMA / DMA; never a mirror wrapper), with goal-only rewards, against each team
+of `--eval-teams`: 'ou' is the wrapper's plain step (the kernel's OU process), 'zero' and 'scripted' are play.py
+teams inside the fused step (set_opponent).  Blue samples its actions as training does, through a FusedPolicy
+of the arena's own over the same Agent.
+
+Counting is unbiased.  For each team every field is reset, `max_episode_length` steps run, and only each
+field's FIRST episode counts: `first = done & ~seen; seen |= done`, and `first` goes to vss_match_tally as one
+group.  Every field finishes by time-out at the latest, so exactly `--eval-fields` episodes are counted per
+team and an episode's chance to be counted does not depend on its length (play_matches' "first n_matches
+episodes to finish" favours short ones).  Nothing reads the device until the team's tally is read once.
+
+An evaluation is a pure function of (weights, --seed, update): before each team's run the env's rng_counter is
+zeroed and the policy's Philox counter is set from the update number.  So the arena owns no state a checkpoint
+must carry -- a resumed run reports the evaluations of the unbroken one -- and it touches nothing of the
+training: not its env, not its policy's counter, not torch's generators (forked around the run).
+"""
+from __future__ import annotations
+
+import time
+
+import torch
+
+from . import _native as N
+
+TEAMS = ("zero", "ou", "scripted")
+
+
+def parse_teams(spec) -> list:
+    """--eval-teams as a list: comma separated names out of TEAMS, each once, at least one."""
+    names = [t.strip() for t in str(spec).split(",") if t.strip()]
+    bad = [t for t in names if t not in TEAMS]
+    if bad or not names or len(set(names)) != len(names):
+        raise ValueError(f"--eval-teams takes distinct names out of {', '.join(TEAMS)}, comma separated; got {spec!r}")
+    return names
+
+
+def score(wins: int, losses: int, episodes: int) -> float:
+    return (wins - losses) / episodes if episodes > 0 else 0.0
+
+
+class Arena:
+    def __init__(self, args, agent, device):
+        from envs.vss import VSS, default_cfg
+        from envs.wrappers import CMA, DMA, SingleAgent
+        from play import get_team
+        from .policy import FusedPolicy
+        self.device = N.require_device(device)
+        self.teams = parse_teams(getattr(args, "eval_teams", ",".join(TEAMS)))
+        n = int(getattr(args, "eval_fields", 1024))
+        if n < 1:
+            raise ValueError(f"--eval-fields must be at least 1, got {n}")
+        if args.env_id not in ("sa", "cma", "dma"):
+            raise ValueError(f"--eval-every needs --env-id sa, cma or dma, got {args.env_id!r}")
+        cfg = default_cfg(n)
+        cfg["env"]["seed"] = int(args.seed) * 1000003 + 500009  # a Philox key of its own (training: seed * 1000003 + rank)
+        with torch.random.fork_rng(devices=[self.device]):
+            env = VSS(cfg=cfg, rl_device=str(self.device), sim_device=str(self.device), graphics_device_id=0, headless=True,
+                      virtual_screen_capture=False, force_render=False)
+            env.w_goal, env.w_grad, env.w_move, env.w_energy = 1.0, 0.0, 0.0, 0.0  # as evaluate() sets them
+            self.env = env
+            self.wrapper = {"sa": SingleAgent, "cma": CMA, "dma": DMA}[args.env_id](env)
+            self.policy = FusedPolicy(agent, seed=int(args.seed) * 7919 + 15485863, actor_only=True)
+        self.opponents = {t: (None if t == "ou" else get_team(t)) for t in self.teams}
+        self.n_fields = n
+        self.rows_per_field = self.wrapper.ROWS_PER_FIELD
+        rows = n * self.rows_per_field
+        self.seen = torch.zeros(rows, dtype=torch.long, device=self.device)
+        self.first = torch.zeros(rows, dtype=torch.long, device=self.device)
+        self.tally = torch.zeros((1, 4), dtype=torch.long, device=self.device)
+        self.steps = int(env.max_episode_length)
+
+    @torch.no_grad()
+    def play(self, team: str, counter: int) -> dict:
+        """Every field's first episode against `team`, the policy's Philox counter starting above `counter`."""
+        env, w, lib = self.env, self.wrapper, N.load()
+        env.rng_counter.zero_()
+        env.reset_buf.fill_(1)
+        env.reset_dones()
+        w.action_buf.zero_()
+        w.set_opponent(self.opponents[team])
+        obs = w.reset()["obs"]
+        self.policy.counter = int(counter)
+        self.seen.zero_()
+        self.tally.zero_()
+        stream = N.stream_of(self.device)
+        for _ in range(self.steps):
+            obs_d, _, dones, info = w.step(self.policy.act(obs))
+            obs = obs_d["obs"]
+            torch.bitwise_and(dones, torch.bitwise_not(self.seen), out=self.first)  # done & ~seen on 0 / 1 int64
+            self.seen.bitwise_or_(dones)
+            N.check(lib.vss_match_tally(stream, self.n_fields, self.rows_per_field, self.n_fields, 1, info["rews"].data_ptr(),
+                                        self.first.data_ptr(), info["progress_buffer"].data_ptr(), self.tally.data_ptr()),
+                    "vss_match_tally")
+        episodes, wins, losses, steps = self.tally[0].tolist()  # the one host read
+        return {"score": score(wins, losses, episodes), "wins": wins, "losses": losses, "draws": episodes - wins - losses,
+                "length": steps / episodes if episodes > 0 else 0.0}
+
+    def evaluate(self, update: int) -> dict:
+        """{team: {score, wins, losses, draws, length}} of the agent's current weights at `update`."""
+        with torch.random.fork_rng(devices=[self.device]):
+            self.policy.refresh()
+            return {t: self.play(t, (int(update) * len(self.teams) + i) * self.steps) for i, t in enumerate(self.teams)}
+
+    def evaluate_into(self, rec: dict, update: int, writer, start_time: float) -> None:
+        """The train loop's call: rec["eval"], rec["eval_s"], the writer's eval/* scalars; rec["wall_s"] and
+        rec["sps"] then include the evaluation, as they include checkpoint_s."""
+        t0 = time.time()
+        rec["eval"] = self.evaluate(update)
+        torch.cuda.synchronize(self.device)
+        rec["eval_s"] = time.time() - t0
+        rec["wall_s"] = time.time() - start_time
+        rec["sps"] = int(rec["global_step"] / rec["wall_s"])
+        for team, r in rec["eval"].items():
+            writer.add_scalar(f"eval/score_{team}", r["score"], rec["global_step"])
+            writer.add_scalar(f"eval/length_{team}", r["length"], rec["global_step"])

@@ -30,9 +30,9 @@ _NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
 
 
 def opponent_mode(value) -> str:
-    """--opponent as a structural value: ou / self / pool / mirror, or 'checkpoint' for any path."""
+    """--opponent as a structural value: ou / self / pool / mirror / scripted, or 'checkpoint' for any path."""
     value = "ou" if value is None else str(value)
-    return value if value in ("ou", "self", "pool", "mirror") else "checkpoint"
+    return value if value in ("ou", "self", "pool", "mirror", "scripted") else "checkpoint"
 
 
 def plain_args(args) -> dict:

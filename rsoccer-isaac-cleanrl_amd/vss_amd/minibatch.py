@@ -548,6 +548,7 @@ def warmup_kernels(args, train) -> float:
     w.num_steps, w.num_updates, w.total_timesteps = 8, 1, 0
     w.log, w.evaluate, w.capture_video, w.track, w.kernel_warmup = False, False, False, False, False
     w.checkpoint_every, w.resume = 0, None  # the throwaway run neither writes a state file nor loads one
+    w.eval_every = 0  # nor builds an arena (--eval-every)
     w.batch_size = int(w.num_envs * w.num_steps)
     w.minibatch_size = int(w.batch_size // w.num_minibatches)
     train(w)

@@ -351,3 +351,41 @@ class OpponentPool:
         if every > 0 and update % every == 0:
             self.add(agent, update)
         return {"versions": self.assign(), "winrate": winrate}
+
+
+def make_opponent(args, agent, fused_env, n_fields: int, seed: int):
+    """The train loop's yellow team for args.opponent, set on the wrapper (set_opponent); None for 'ou' (the
+    kernel's OU process stays) and 'mirror' (both teams' robots are learner rows: no snapshot, no sync, no
+    opponent forward).  `seed`: the Philox seed of the opponent's own stream.  With args.kernel_warmup a policy
+    opponent runs one forward at this run's own row count outside the clock (under 16,384 opponent rows it is
+    the actor-only fused kernel, which the 16,384-env warm-up run does not reach); its Philox counter is put
+    back, so the training's draws do not change."""
+    mode = getattr(args, "opponent", "ou")
+    if mode in ("ou", "mirror"):
+        return None
+    if mode == "scripted":
+        # the scripted benchmark team: a pure function of the yellow observations, one launch per step -- no
+        # snapshot, no sync, no warm-up forward; its state dict holds the controller's version alone
+        from play import TeamScripted
+        opponent = TeamScripted()
+        fused_env.set_opponent(opponent)
+        return opponent
+    if mode == "pool":
+        # a league of past snapshots, each on its slice of this rank's fields; the match tallies -- and so the
+        # assignments -- are per rank
+        opponent = OpponentPool(agent, KIND_OF_ENV[args.env_id], n_fields, slots=getattr(args, "opponent_pool_slots", 8),
+                                capacity=getattr(args, "opponent_pool_size", 16),
+                                latest=getattr(args, "opponent_pool_latest", 0.5),
+                                pfsp_power=getattr(args, "opponent_pfsp_power", 1.0), seed=seed)
+        counted = opponent
+    else:
+        opponent = SnapshotOpponent(agent, KIND_OF_ENV[args.env_id], seed=seed)
+        if mode != "self":
+            opponent.load(mode)
+        counted = opponent.policy
+    fused_env.set_opponent(opponent)
+    if getattr(args, "kernel_warmup", False):
+        counter = counted.counter
+        opponent(torch.zeros_like(fused_env._opp_act), fused_env._opp_obs)
+        counted.counter = counter
+    return opponent
