@@ -718,6 +718,55 @@ int vss_match_tally(void* stream, int64_t n_fields, int32_t rows_per_field, int6
 int vss_scripted_team(void* stream, int64_t n_fields, int32_t version, const float* obs, int64_t obs_field_stride,
                       float* act, int64_t act_field_stride);
 
+/* ---------------------------------------------------------------------------------------------
+ * The perception channel (csrc/vss_perceive.hip; vss_amd/perceive.py): what an overhead
+ * camera hands a policy instead of the simulator's state -- observation rows `delay` control steps late
+ * and with Gaussian noise on every pose -- in one launch per call.  vss_amd.perceive.reference_perceive
+ * specifies it operation by operation and the kernel equals it bit for bit.
+ *
+ * Rows: the 52-float row of team block b, field f, robot k is at
+ *   base + (b * team_stride + f * field_stride + k) * 52 floats
+ * for obs, term, obs_out and term_out alike; block b's team is first_team ^ b (0 blue, 1 yellow).
+ * State (the caller's, zero-initialised or not: a start call initialises it):
+ *   ring (delay + 1, n_teams, n_fields, robots, 52) fp32: the last delay + 1 true `obs` frames, the frame
+ *     of call t in slot t % (delay + 1);  age (n_fields) int32: steps since the field's episode began,
+ *     saturating at delay.
+ * One call, per field (done = done[f * done_stride] != 0):
+ *   d = min(age + 1, delay);  R = ring frame call - d (delay >= 1)
+ *   term_out = R with the six own-action floats (11, 12, 20, 21, 29, 30) of `term`;  `term` itself for delay 0
+ *   age' = done ? 0 : d;  ring slot call % (delay + 1) = obs
+ *   obs_out = age' == 0 ? obs : R with the six own-action floats of `obs`
+ *   then the same noise on both outputs: one set of 40 unit normals per (field, call) -- Philox4x32-10,
+ *   key (seed low, seed high), counter (field, call, 7 << 24, block 0..9), Box-Muller as the step's OU
+ *   draws -- scaled by the class's sigma: positions (m), velocities (m/s), headings (rad, a rotation of
+ *   (cos, sin)) and yaw rates (rad/s) of the ball and the six robots in the world frame, so every row
+ *   of a field sees the same world.  A class with sigma 0 is copied unchanged.
+ * term == NULL (and term_out == NULL) is the start call of reset(): age = 0, the slot is written,
+ * obs_out = obs + noise.  No frame of an earlier episode is ever read.
+ * call: the caller's call index, +1 per call; the slot and the frame arithmetic are modulo delay + 1.
+ *
+ * VSS_E_ARG, before any HIP call: a null lay, noise, obs, done, ring, age or obs_out; exactly one of term /
+ * term_out null; a row pointer not 16-B, done not 8-B or age not 4-B aligned; an output (obs_out, term_out,
+ * ring, age) overlapping an input or another output; delay outside 0..VSS_PERCEIVE_MAX_DELAY; a negative or
+ * non-finite sigma; robots not 1 or 3; n_teams not 1 or 2; first_team not 0 or 1; field_stride < robots;
+ * with two teams team_stride < (n_fields - 1) * field_stride + robots; done_stride < 1; n_fields < 0; sizes
+ * whose grid or byte offsets overflow.  n_fields == 0: VSS_OK, no launch.
+ * ------------------------------------------------------------------------------------------- */
+#define VSS_PERCEIVE_MAX_DELAY 15
+typedef struct vss_perceive_layout {
+  int64_t field_stride;  /* rows from field f to f+1 within a team block               */
+  int64_t team_stride;   /* rows from team block 0 to block 1 (n_teams == 2)           */
+  int32_t robots;        /* rows per field and team, 1 or 3; row k is robot k          */
+  int32_t n_teams;       /* 1 or 2                                                     */
+  int32_t first_team;    /* team of block 0: 0 blue, 1 yellow; block 1 is the other    */
+} vss_perceive_layout;
+typedef struct vss_perceive_noise { float pos, vel, ang, angvel; } vss_perceive_noise;
+int vss_perceive(void* stream, int64_t n_fields, const vss_perceive_layout* lay, int32_t delay,
+                 const vss_perceive_noise* noise, uint64_t seed, uint32_t call,
+                 const float* obs, const float* term /* NULL: start */, const int64_t* done, int64_t done_stride,
+                 float* ring /* (delay+1, n_teams, n_fields, robots, 52) */, int32_t* age /* (n_fields) */,
+                 float* obs_out, float* term_out /* NULL iff term is */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,7 +71,36 @@ def make_env(args):
     elif opponent != "ou" and not (opponent in ("self", "pool", "scripted") or os.path.exists(opponent)):
         raise ValueError(f"--opponent must be ou, self, pool, mirror, scripted or a checkpoint path, got {opponent!r}")
     # the opponent itself (a snapshot of the Agent) is set by the train loop: set_opponent()
-    return envs, wrappers[args.env_id](envs)
+    wrapped = wrappers[args.env_id](envs)
+    delay, noise = perception_args(args)
+    if delay or noise.any():  # --obs-delay / --obs-noise-*: with all of them zero the chain is as without the flags
+        wrapped = Perceived(wrapped, delay, noise, perception_seed(getattr(args, "seed", None)))
+    return envs, wrapped
+
+
+def perception_args(args):
+    """(delay, Noise) of --obs-delay and --obs-noise-pos / -vel / -ang / -angvel; absent flags are zero."""
+    from vss_amd.perceive import Noise
+    return int(getattr(args, "obs_delay", 0) or 0), Noise(*(float(getattr(args, f"obs_noise_{k}", 0.0) or 0.0)
+                                                           for k in ("pos", "vel", "ang", "angvel")))
+
+
+def perception_seed(seed, offset: int = 0) -> int:
+    """The channel's Philox key from --seed and the rank, with a constant of its own (the env's key is
+    seed * 1000003 + rank); `offset` separates the arena's channel from the training's."""
+    return (int(seed or 0) * 1000003 + int(os.environ.get("RANK", 0))) * 2654435761 + 0x5EE1_0B5E + int(offset)
+
+
+def evaluation_channel(args, env, offset: int = 2):
+    """evaluate()'s channel over the blue rows of the raw env's FULL layout (play.play_matches), with a key of its
+    own; None when the perception flags are all zero."""
+    from vss_amd import perceive as P
+    delay, noise = perception_args(args)
+    if not (delay or noise.any()):
+        return None
+    n = env.num_fields
+    return P.PerceptionChannel(n, P.layout_full_blue(), delay, noise, perception_seed(getattr(args, "seed", None), offset),
+                               env.device, rows=n * 6)
 
 
 class RecordEpisodeStatisticsTorch(Wrapper):
@@ -262,6 +291,105 @@ class DMA(_FusedWrapper):
         super().__init__(env)
         self._action_space = Box(-1.0, 1.0, (env.num_actions,))
         self._observation_space = Box(-np.inf, np.inf, (env.num_obs,))
+
+
+class _PerceivedTeam:
+    """A policy team behind the yellow channel: it acts on the perceived opponent rows, whatever rows the
+    step hands it; everything else (check_env, observe, state, version ...) is the team's own."""
+
+    def __init__(self, team, channel):
+        self.team, self.channel = team, channel
+
+    def __call__(self, act, obs):
+        self.team(act, self.channel.obs_out.view(obs.shape))
+
+    def __getattr__(self, name):
+        if name in ("team", "channel"):  # not set yet (a copy under construction): no forwarding loop
+            raise AttributeError(name)
+        return getattr(self.team, name)
+
+
+class Perceived(Wrapper):
+    """Observation latency and vision noise round an SA / CMA / DMA or mirror wrapper (vss_amd/perceive.py,
+    DESIGN.md §17): `obs` and info["terminal_observation"] become what an overhead camera would have delivered --
+    `delay` steps late, Gaussian noise on every pose -- by one vss_perceive launch per step.  Rewards, dones and
+    every other info pass through, and the step itself reads and writes the true rows.
+
+    A policy opponent trained on perceived rows (--opponent self, pool or a checkpoint) acts on the output of a
+    second channel over the versus step's opp_obs: the same seed and call index, so both teams see one world.
+    The scripted team, zero and the kernel's OU process see the truth; info["opponent_obs"] stays true."""
+
+    def __init__(self, env, delay: int, noise, seed: int):
+        super().__init__(env)
+        from vss_amd import perceive as P
+        vss = env.env
+        n = vss.num_fields
+        mirror = isinstance(env, _MirrorWrapper)
+        if mirror:
+            layout, stride = P.layout_mirror(env.FIELD_ROWS, n), env.FIELD_ROWS
+        elif env.ROWS_PER_FIELD == 3:
+            layout, stride = P.layout_dma(), 3
+        else:
+            layout, stride = P.layout_sa(), 1
+        self.delay, self.noise, self.seed = int(delay), P.Noise(*noise), int(seed)
+        self.channel = P.PerceptionChannel(n, layout, self.delay, self.noise, self.seed, vss.device, done_stride=stride)
+        self.opponent_channel = None
+        self.channel.start(env._obs)  # as the inner wrapper's constructor computes its first observation
+
+    @property
+    def _opp_obs(self):
+        return self.env._opp_obs
+
+    @property
+    def _opp_act(self):
+        return self.env._opp_act
+
+    def set_opponent(self, team=None, perceived=None):
+        """The inner wrapper's set_opponent; `perceived` (default: a SnapshotOpponent or an OpponentPool, i.e.
+        a policy that was trained on perceived rows) puts the yellow channel in front of the team."""
+        from vss_amd import perceive as P
+        from vss_amd.opponent import OpponentPool, SnapshotOpponent
+        if perceived is None:
+            perceived = isinstance(team, (SnapshotOpponent, OpponentPool))
+        if team is None or not perceived:
+            self.env.set_opponent(team)
+            self.opponent_channel = None
+            return
+        vss = self.env.env
+        ch = P.PerceptionChannel(vss.num_fields, P.layout_opponent(), self.delay, self.noise, self.seed, vss.device,
+                                 done_stride=self.channel.done_stride)
+        self.env.set_opponent(_PerceivedTeam(team, ch))
+        self.opponent_channel = ch
+        ch.start(self.env._opp_obs, call=max(self.channel.call - 1, 0))  # the learner's rows' last call: one world
+
+    def reset(self, **kwargs):
+        obs = self.env.reset(**kwargs)["obs"]
+        if self.opponent_channel is not None:
+            self.opponent_channel.start(self.env._opp_obs)
+        return {"obs": self.channel.start(obs)}
+
+    def step(self, action):
+        obs, reward, dones, infos = self.env.step(action)
+        p_obs, p_term = self.channel.perceive(obs["obs"], infos["terminal_observation"], dones)
+        if self.opponent_channel is not None:
+            # no terminal row on the yellow side: the true rows stand in and the second output is not used
+            self.opponent_channel.perceive(self.env._opp_obs, self.env._opp_obs, dones)
+        infos = dict(infos, terminal_observation=p_term)
+        return {"obs": p_obs}, reward, dones, infos
+
+    def state_dict(self) -> dict:
+        """The inner wrapper's state and the channels' (ring, age, outputs, call), on the CPU."""
+        out = {"inner": self.env.state_dict(), "channel": self.channel.state_dict()}
+        if self.opponent_channel is not None:
+            out["opponent_channel"] = self.opponent_channel.state_dict()
+        return out
+
+    def load_state_dict(self, state: dict) -> None:
+        from vss_amd.checkpoint import entry
+        self.env.load_state_dict(entry(state, "inner", "Perceived"))
+        self.channel.load_state_dict(entry(state, "channel", "Perceived"))
+        if self.opponent_channel is not None:
+            self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Perceived"))
 
 
 class _MirrorWrapper(Wrapper):

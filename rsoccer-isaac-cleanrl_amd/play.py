@@ -132,14 +132,17 @@ def baseline_teams(root="base_nets", device="cuda:0"):
 
 
 @torch.no_grad()
-def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk=32):
-    """Mean blue goal score and episode length over the first `n_matches` finished episodes."""
+def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk=32, perceive=None):
+    """Mean blue goal score and episode length over the first `n_matches` finished episodes.  `perceive`: a
+    vss_amd.perceive.PerceptionChannel over the blue rows of the FULL layout (layout_full_blue, rows = 6 N);
+    blue then acts on what the camera would have delivered, yellow on the truth."""
     envs.reset_buf[:] = 1
     envs.reset_dones()  # like the reference, obs_buf is not recomputed here (play.py:132-151)
     n = envs.num_fields
     k = min(COUNT_FIELDS, n)
     action_buf = torch.zeros((n,) + tuple(envs.action_space.shape), device=envs.device)
     obs = envs.reset()["obs"]
+    blue_obs = obs if perceive is None else perceive.start(obs)
     rec = None
     if video_path:  # play.py:134-142: the first 300 steps of field 0 (envs/render.py, GIF)
         from envs.render import FrameRecorder
@@ -150,12 +153,14 @@ def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk
         rsum = torch.zeros(chunk, device=envs.device, dtype=torch.float64)
         lsum = torch.zeros(chunk, device=envs.device, dtype=torch.float64)
         for t in range(chunk):
-            blue_team(action_buf[:, 0], obs[:, 0])
+            blue_team(action_buf[:, 0], blue_obs[:, 0])
             yellow_team(action_buf[:, 1], obs[:, 1])
             o, rew, dones, info = envs.step(action_buf)
             if rec is not None:
                 rec.on_step()
             obs = o["obs"]
+            # (no terminal row is used here: the true rows stand in for it)
+            blue_obs = obs if perceive is None else perceive.perceive(obs, obs, dones)[0]
             d = dones[:k] != 0
             cnt[t] = d.sum()
             rsum[t] = (rew[:k, 0, 0, 0] * d).sum()

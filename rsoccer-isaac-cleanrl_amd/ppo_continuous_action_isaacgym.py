@@ -29,6 +29,8 @@ the loop -- and the machinery under it lives in vss_amd/:
   learner rows, two per field (dma: six);
 * `--opponent scripted` (a build addition): the yellow team is the scripted benchmark team (vss_amd/scripted.py,
   one vss_scripted_team launch per step) -- a fixed opponent that plays, with nothing to snapshot or sync;
+* `--obs-delay D --obs-noise-pos|vel|ang|angvel S` (a build addition): the learner and a policy opponent see rows D steps
+  late with Gaussian noise on every pose (vss_amd/perceive.py); all zero (the default): no wrapper, no launch;
 * `--eval-every K` (a build addition): every K-th update rank 0 plays the live agent against fixed teams on a
   separate arena env (vss_amd/arena.py) and adds the scores to the update's record; the training's bits do not move.
 """
@@ -148,6 +150,9 @@ def parse_args(argv=None):
                    help="--opponent pool: the share of the slots that plays the newest snapshot")
     p.add_argument("--opponent-pfsp-power", type=float, default=1.0,
                    help="--opponent pool: the other slots draw a snapshot with probability ~ (1 - win rate) ** power")
+    p.add_argument("--obs-delay", type=int, default=0, help="observations this many control steps late (0..15; Perceived)")
+    for k, what in (("pos", "position (m)"), ("vel", "velocity (m/s)"), ("ang", "heading (rad)"), ("angvel", "yaw rate (rad/s)")):
+        p.add_argument(f"--obs-noise-{k}", type=float, default=0.0, help=f"vision noise: std of every {what}; 0: none")
     p.add_argument("--checkpoint-every", type=int, default=0, help="every K-th update: <run>-state.pt, <run>-agent-u<update>.pt")
     p.add_argument("--resume", type=str, default=None, help="a <run>-state.pt: go on after its update, bit-equal (DESIGN.md §15)")
     args = p.parse_args(argv)
@@ -344,7 +349,9 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
     the reference's Validation/* names and are returned.  The scripted team (a build addition) is played and
     reported too, as Validation/Score/scripted and Validation/Length/scripted, outside Score Mean / Length
     Mean: those stay over the reference's teams."""
+    from envs.wrappers import evaluation_channel
     from play import baseline_teams, get_team, play_matches
+    perceive = evaluation_channel(args, unwrapped_env)  # --obs-*: blue sees perceived rows as in training; else None
     unwrapped_env.w_goal, unwrapped_env.w_grad, unwrapped_env.w_move, unwrapped_env.w_energy = 1.0, 0.0, 0.0, 0.0
     device = unwrapped_env.device
     teams = baseline_teams(device=str(device))
@@ -357,7 +364,7 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
         for team, seeds in teams.items():
             t_score = t_len = 0.0
             for seed, yellow in seeds.items():
-                r, ln = play_matches(unwrapped_env, blue, yellow, args.eval_matches)
+                r, ln = play_matches(unwrapped_env, blue, yellow, args.eval_matches, perceive=perceive)
                 t_score += r
                 t_len += ln
                 scores.append(r)
@@ -367,7 +374,7 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
         res["Validation/Score Mean"] = sum(scores) / len(scores)
         res["Validation/Length Mean"] = sum(lengths) / len(lengths)
         res["Validation/Score/scripted"], res["Validation/Length/scripted"] = play_matches(
-            unwrapped_env, blue, get_team("scripted"), args.eval_matches)
+            unwrapped_env, blue, get_team("scripted"), args.eval_matches, perceive=perceive)
         for k, v in res.items():
             writer.add_scalar(f"{algo}/{k}", v, global_step)
         print(f"evaluation {algo}: " + ", ".join(f"{k} {v:.3f}" for k, v in res.items()), flush=True)

@@ -42,7 +42,7 @@ STAMPED = (os.path.join(CSRC, "vss_step.hip"), os.path.join(CSRC, "vss_update.hi
            os.path.join(CSRC, "vss_policy.hip"), os.path.join(CSRC, "vss_gemm_x6.hip"),
            os.path.join(CSRC, "vss_loss.hip"), os.path.join(CSRC, "vss_optim.hip"),
            os.path.join(CSRC, "vss_returns.hip"), os.path.join(CSRC, "vss_scripted.hip"),
-           os.path.join(CSRC, "vss_loss_row.h"), HEADER,
+           os.path.join(CSRC, "vss_perceive.hip"), os.path.join(CSRC, "vss_loss_row.h"), HEADER,
            os.path.join(CSRC, "Makefile"))
 
 ABI_VERSION = 2
@@ -67,7 +67,7 @@ EXPORTED = ("vss_abi_version", "vss_source_hash", "vss_error_string", "vss_step"
             "vss_ppo_loss_direct", "vss_minibatch_gather_parts", "vss_minibatch_gather", "vss_adv_part_sum",
             "vss_first_layer_bf16x6", "vss_linear_tanh_loss_blocks_bf16x6", "vss_linear_tanh_loss_bf16x6",
             "vss_ppo_loss_fused_finish", "vss_randperm_scratch_bytes", "vss_randperm", "vss_randperm_bits",
-            "vss_gae", "vss_scripted_team")
+            "vss_gae", "vss_scripted_team", "vss_perceive")
 
 
 class VssParams(ctypes.Structure):
@@ -102,6 +102,20 @@ class VssMirrorIO(ctypes.Structure):
     """The yellow team's learner rows of vss_step_mirror (include/vss.h vss_mirror_io)."""
     _fields_ = [(k, ctypes.c_void_p) for k in
                 ("actions", "obs", "terminal_obs", "rew", "reward_sum", "dones", "time_outs", "progress_f")]
+
+
+PERCEIVE_MAX_DELAY = 15
+
+
+class VssPerceiveLayout(ctypes.Structure):
+    """Where the rows of vss_perceive lie (include/vss.h vss_perceive_layout), strides in 52-float rows."""
+    _fields_ = [("field_stride", ctypes.c_int64), ("team_stride", ctypes.c_int64), ("robots", ctypes.c_int32),
+                ("n_teams", ctypes.c_int32), ("first_team", ctypes.c_int32)]
+
+
+class VssPerceiveNoise(ctypes.Structure):
+    """The four standard deviations of vss_perceive (include/vss.h vss_perceive_noise)."""
+    _fields_ = [(k, ctypes.c_float) for k in ("pos", "vel", "ang", "angvel")]
 
 
 MAX_ACTOR_GROUPS = 16
@@ -287,6 +301,8 @@ def load() -> ctypes.CDLL:
     L.vss_gae.restype = ctypes.c_int
     L.vss_scripted_team.argtypes = [P, i64, i32, P, i64, P, i64]
     L.vss_scripted_team.restype = ctypes.c_int
+    L.vss_perceive.argtypes = [P, i64, P, i32, P, ctypes.c_uint64, ctypes.c_uint32, P, P, P, i64, P, P, P, P]
+    L.vss_perceive.restype = ctypes.c_int
     if L.vss_abi_version() != ABI_VERSION:
         raise NativeError(f"libvss_amd ABI {L.vss_abi_version()} != expected {ABI_VERSION}")
     _lib = L

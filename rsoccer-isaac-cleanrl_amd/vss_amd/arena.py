@@ -62,6 +62,12 @@ class Arena:
             env.w_goal, env.w_grad, env.w_move, env.w_energy = 1.0, 0.0, 0.0, 0.0  # as evaluate() sets them
             self.env = env
             self.wrapper = {"sa": SingleAgent, "cma": CMA, "dma": DMA}[args.env_id](env)
+            # --obs-delay / --obs-noise-*: blue sees perceived rows as in training, through a channel of the arena's
+            # own (a key of its own); reset() starts it afresh at call 0 in every play, so it carries no state over
+            from envs.wrappers import Perceived, perception_args, perception_seed
+            delay, noise = perception_args(args)
+            if delay or noise.any():
+                self.wrapper = Perceived(self.wrapper, delay, noise, perception_seed(args.seed, 1))
             self.policy = FusedPolicy(agent, seed=int(args.seed) * 7919 + 15485863, actor_only=True)
         self.opponents = {t: (None if t == "ou" else get_team(t)) for t in self.teams}
         self.n_fields = n

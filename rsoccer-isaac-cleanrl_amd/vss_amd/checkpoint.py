@@ -25,6 +25,9 @@ FORMAT_VERSION = 1
 # equal the saved ones (the seed too: the env's Philox key and the policies' seeds are rebuilt from it)
 STRUCTURAL = ("env_id", "num_envs", "num_steps", "seed", "opponent", "opponent_pool_slots", "opponent_pool_size",
               "fused_policy", "amp", "cuda")
+# the perception channel's flags (vss_amd/perceive.py): structural as well -- the ring's depth and the set of state
+# owners follow them -- and absent from a state file written before they existed, where they count as zero
+PERCEPTION_STRUCTURAL = ("obs_delay", "obs_noise_pos", "obs_noise_vel", "obs_noise_ang", "obs_noise_angvel")
 # set by train() itself or about the checkpoint, not hyper-parameters: never reported as changed
 _NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
 
@@ -46,10 +49,12 @@ def check_compatible(saved_args, args, log=print) -> list:
     ValueError naming the key and both values; every other argument is taken from `args`, and each one that
     differs from the saved value is reported once through `log` (None: silent).  Returns the changed keys."""
     saved, new = plain_args(saved_args), plain_args(args)
-    for k in STRUCTURAL:
+    for k in STRUCTURAL + PERCEPTION_STRUCTURAL:
         a, b = saved.get(k), new.get(k)
         if k == "opponent":
             a, b = opponent_mode(a), opponent_mode(b)
+        if k in PERCEPTION_STRUCTURAL:
+            a, b = a or 0, b or 0
         if a != b:
             raise ValueError(f"--resume: {k} is structural and differs: the state file has {a!r}, this command line {b!r}")
     changed = []
