@@ -497,16 +497,106 @@ __device__ __forceinline__ void coop_load(const float* __restrict__ g, int nv, f
   }
 }
 
+// ---- wave-cooperative 16-B stores with a cache policy ---------------------------------------------
+// The streams go out through a buffer resource over exactly the wave's output block (base and size
+// wave-uniform: blockIdx and kernel arguments only, so the descriptor sits in SGPRs with no waterfall
+// loop; a block is at most kFpw x 312 floats, so its size fits 32 bits for any n).  The range check
+// drops a store past the block, so the streams need no per-lane predicate, and the builtin's `aux`
+// argument carries the cache policy (gfx940+ encoding: 2 = nt, 16 = sc1):
+//   plain   the line stays in the XCD's L2, dirty, until it is evicted or the kernel's end writes it back
+//   nt      the same, marked for early eviction
+//   wt      write-through (sc1): the bytes leave the L2 while the kernel still runs, the line is dropped
+//   wtnt    both bits
+// Why it matters: DESIGN.md §5.1, "the launch's end".  The policy of each store group is a 2-bit field
+// of StepArgs::store_policy (wave-uniform), set by the host from (mode, footprint) in launch_step.
+enum : uint32_t { kStPlain = 0, kStNt = 1, kStWt = 2, kStWtNt = 3 };
+// store groups: bit position of the group's policy in the policy word
+enum : uint32_t { kGrpTerminal = 0, kGrpObs = 2, kGrpYellow = 4, kGrpState = 6, kGrpAos = 8 };
+constexpr uint32_t policy_word(uint32_t terminal, uint32_t obs, uint32_t yellow, uint32_t state, uint32_t aos) {
+  return terminal << kGrpTerminal | obs << kGrpObs | yellow << kGrpYellow | state << kGrpState | aos << kGrpAos;
+}
+__device__ __forceinline__ uint32_t policy_of(uint32_t word, uint32_t grp) { return (word >> grp) & 3u; }
+
+using BufRsrc = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ BufRsrc wave_rsrc(void* base, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)bytes, 0x00020000);
+}
+
+// one 16-B store at byte offset `off` of the resource, policy POL
+template <uint32_t POL>
+__device__ __forceinline__ void store16(BufRsrc r, uint32_t off, float4 v) {
+  typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+  constexpr int aux = POL == kStNt ? 2 : POL == kStWt ? 16 : POL == kStWtNt ? 18 : 0;
+  const u4v d = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(d, r, (int)off, 0, aux);
+}
+
+// f(policy as a constant) for the wave-uniform `pol`: the callers put a whole burst of stores into f, so the
+// scalar branch is paid once per burst (a switch around each store measured 1.4-3 % slower per step)
+template <class F>
+__device__ __forceinline__ void with_policy(uint32_t pol, F f) {
+  switch (pol) {
+    case kStNt: f(std::integral_constant<uint32_t, kStNt>{}); break;
+    case kStWt: f(std::integral_constant<uint32_t, kStWt>{}); break;
+    case kStWtNt: f(std::integral_constant<uint32_t, kStWtNt>{}); break;
+    default: f(std::integral_constant<uint32_t, kStPlain>{}); break;
+  }
+}
+
+// The state's 46 live channels of a full wave (kFpw fields) as 16-B stores: the writer lanes put
+// their channels into the LDS records (stride kRec), then the whole wave writes each channel's 128
+// contiguous bytes as 8 lanes x 16 B -- 46 x 8 = 368 stores, six wave-instructions instead of 46
+// half-wave 4-byte ones (a 4-byte write-through store costs about six times a 16-byte one per byte).
+// One resource from the wave's first field of channel 0 to its last field of the last channel; the
+// caller keeps n <= 2^23, so every offset stays below 2^31.  The channel stride is n floats, so for
+// an n that is no multiple of 4 these stores are 4-byte aligned only, which the buffer path takes.
+// Ends with a barrier: the records are free again.
+__device__ __forceinline__ void store_bodies_wave(float* __restrict__ st, int64_t n, int64_t f0, const Bodies& b,
+                                                  float* lds, int lane, bool writer, uint32_t pol) {
+  constexpr int kLive = VSS_STATE_CHANNELS - (VSS_CH_RQZ - VSS_CH_RQX);
+  static_assert(kLive <= kRec && kFpw == 32, "one record per field, eight 16-B pieces per channel");
+  if (writer) {
+    float* r = lds + lane * kRec;  // live channel ci: state channel ci (ci < RQX) or ci + (RQZ - RQX)
+    r[VSS_CH_BALL_X] = b.bx; r[VSS_CH_BALL_Y] = b.by; r[VSS_CH_BALL_VX] = b.bvx; r[VSS_CH_BALL_VY] = b.bvy;
+    constexpr int D = VSS_CH_RQZ - VSS_CH_RQX;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      r[VSS_CH_RX + i] = b.x[i]; r[VSS_CH_RY + i] = b.y[i];
+      r[VSS_CH_RQZ - D + i] = b.qz[i]; r[VSS_CH_RQW - D + i] = b.qw[i];
+      r[VSS_CH_RVX - D + i] = b.vx[i]; r[VSS_CH_RVY - D + i] = b.vy[i]; r[VSS_CH_RW - D + i] = b.w[i];
+    }
+  }
+  __syncthreads();
+  const uint32_t un = (uint32_t)n;
+  const BufRsrc rs = wave_rsrc(st + f0, 4u * ((uint32_t)(VSS_STATE_CHANNELS - 1) * un + (uint32_t)kFpw));
+  with_policy(pol, [&](auto P) {
+#pragma unroll
+    for (int i = 0; i < (kLive * 8 + kWave - 1) / kWave; ++i) {
+      const int s = lane + i * kWave, ci = s >> 3, part = s & 7;
+      if (ci < kLive) {
+        const uint32_t c = (uint32_t)(ci < VSS_CH_RQX ? ci : ci + (VSS_CH_RQZ - VSS_CH_RQX));
+        const float* src = lds + (part * 4) * kRec + ci;
+        store16<decltype(P)::value>(rs, 4u * (c * un) + 16u * (uint32_t)part,
+                                    make_float4(src[0], src[kRec], src[2 * kRec], src[3 * kRec]));
+      }
+    }
+  });
+  __syncthreads();
+}
+
 template <int W>
-__device__ __forceinline__ void coop_store(float* __restrict__ g, int nv, const float* lds, int lane) {
+__device__ __forceinline__ void coop_store(float* __restrict__ g, int nv, const float* lds, int lane,
+                                           uint32_t pol = kStPlain) {
   const int total = nv * W;
   if constexpr (W % 4 == 0) {
-    float4* g4 = reinterpret_cast<float4*>(g);
-    for (int q = lane; q < total / 4; q += kWave) {
-      int e = q * 4, fl = e / W, k = e - fl * W;
-      const float* s = lds + fl * kRec + k;
-      at(g4, 16u * (uint32_t)q) = make_float4(s[0], s[1], s[2], s[3]);
-    }
+    const BufRsrc rs = wave_rsrc(g, 4u * (uint32_t)total);
+    with_policy(pol, [&](auto P) {
+      for (int q = lane; q < total / 4; q += kWave) {
+        int e = q * 4, fl = e / W, k = e - fl * W;
+        const float* s = lds + fl * kRec + k;
+        store16<decltype(P)::value>(rs, 16u * (uint32_t)q, make_float4(s[0], s[1], s[2], s[3]));
+      }
+    });
   } else {
     float2* g2 = reinterpret_cast<float2*>(g);
     for (int q = lane; q < total / 2; q += kWave) {
@@ -546,24 +636,23 @@ __device__ __forceinline__ void write_obs_record(float* rec, const Bodies& b, co
 // lane walks float4 slots q = lane, lane + 64, ... with its (field, slot) position advanced
 // incrementally; four LDS reads per float4 at table-given byte offsets, one 16-B store.  Unrolled
 // by kObsUnroll so the LDS latency of U slots overlaps (reads past the last field are clamped to
-// the last record and their stores predicated off).
+// the last record and their stores dropped by the resource's range check).
 //
-// nt: nontemporal stores (profiles/r02_ablate_nt_obs.log).  The wrapped modes' steps are 2-5 %
-// faster with both observation streams nontemporal (SA 21.3 -> 20.5 us, CMA 21.5 -> 20.4, DMA
-// 28.4 -> 27.7).  The FULL step streams 164 MB of observations per 65,536 fields: while its whole
-// footprint fits the 256 MiB Infinity Cache plain stores are best (both streams nontemporal: 11 %
-// slower, one: +0.5 %); past it, one stream nontemporal and the other plain is best (131,072
-// fields: 74.5 -> 68.4 us; both nontemporal: +1.6 % only), so the host sets StepArgs::nt_obs for
-// footprints above the cache size and FULL then streams `obs` nontemporally, `terminal_obs` plain.
-// The K-step rollout (K x 175 MB per launch) streams both nontemporally: 36.1 -> 33.3 us per step at
-// K = 16 (obs alone: no gain).
+// pol: the stream's cache policy (store_policy on the host).  While the step's footprint fits the 256 MiB
+// Infinity Cache both streams are write-through (profiles/step_wt_bench.json: FULL 40.2 -> 36.2 us at
+// 65,536 fields, the wrapped modes 3-6 %).  Before that (profiles/r02_ablate_nt_obs.log) the wrapped
+// modes' streams were nontemporal (2-5 % over plain) and FULL's plain (both nontemporal: 11 % slower).
+// Past the cache write-through loses (131,072 fields: 77 against 73 us) and the older table holds: FULL
+// streams `obs` nontemporally and `terminal_obs` plain (74.5 -> 68.4 us; both nontemporal: +1.6 % only),
+// the wrapped modes both nontemporally.  The K-step rollout (K x 175 MB per launch) streams both
+// nontemporally: 36.1 -> 33.3 us per step at K = 16 (obs alone: no gain).
 //
 // A0, REC (the versus step): agents [A0, A0 + A) of the table out of records of REC floats -- the
 // learner's block (A0 = 0) and the yellow team's (A0 = 3) both come from one kRecObs6 record.
 constexpr int kObsUnroll = 4;
 template <int A, int A0 = 0, int REC = obs_rec<A>()>
 __device__ __forceinline__ void coop_store_obs(float* __restrict__ out, int nv, const float* lds, const uint32_t* tab,
-                                               int lane, bool nt = false) {
+                                               int lane, uint32_t pol = kStPlain) {
   static_assert(A0 + A <= 6 && (A0 == 0 || REC == kRecObs6), "yellow agents read the mirror slots");
   constexpr int Q = 13 * A;  // float4 per field
   constexpr int QD = kWave / Q, QR = kWave % Q;
@@ -573,8 +662,10 @@ __device__ __forceinline__ void coop_store_obs(float* __restrict__ out, int nv, 
   int fl = lane / Q, j4 = lane - fl * Q;
   uint32_t rb = (uint32_t)fl * RB;
   const char* L = reinterpret_cast<const char*>(lds);
-  float4* o4 = reinterpret_cast<float4*>(out);
-  for (int q0 = lane; q0 < total; q0 += kObsUnroll * kWave) {
+  const BufRsrc rs = wave_rsrc(out, 16u * (uint32_t)total);  // the wave's block: stores past it are dropped
+  // a wave-uniform trip count: every lane runs every slot, the range check predicates the stores
+  for (int base = 0; base < total; base += kObsUnroll * kWave) {
+    const int q0 = base + lane;
     float4 v[kObsUnroll];
 #pragma unroll
     for (int u = 0; u < kObsUnroll; ++u) {
@@ -588,17 +679,10 @@ __device__ __forceinline__ void coop_store_obs(float* __restrict__ out, int nv, 
       rb += QD * RB;
       if (j4 >= Q) { j4 -= Q; rb += RB; }
     }
+    with_policy(pol, [&](auto P) {  // one scalar branch per kObsUnroll stores
 #pragma unroll
-    for (int u = 0; u < kObsUnroll; ++u)
-      if (q0 + u * kWave < total) {
-        if (nt) {  // wave-uniform
-          typedef float f4v __attribute__((ext_vector_type(4)));
-          __builtin_nontemporal_store(f4v{v[u].x, v[u].y, v[u].z, v[u].w},
-                                      reinterpret_cast<f4v*>(&at(o4, 16u * (uint32_t)(q0 + u * kWave))));
-        } else {
-          at(o4, 16u * (uint32_t)(q0 + u * kWave)) = v[u];
-        }
-      }
+      for (int u = 0; u < kObsUnroll; ++u) store16<decltype(P)::value>(rs, 16u * (uint32_t)(q0 + u * kWave), v[u]);
+    });
   }
 }
 
@@ -927,7 +1011,7 @@ struct StepArgs {
   vss_step_io io;
   vss_replay_draws rd;  // REPLAY instantiations only (vss_step_replay)
   uint32_t rd_rounds;   // rejection rounds one replay row holds
-  uint32_t nt_obs;      // FULL: stream obs with nontemporal stores (footprint past the Infinity Cache)
+  uint32_t store_policy;  // cache policy of each store group (policy_word), set by launch_step
 };
 
 template <int MODE>
@@ -959,7 +1043,7 @@ __device__ __forceinline__ void load_batch(const StepArgs& args, int64_t f0, int
 //   * the terminal record skips the mirror slots (the learner's rows only), the record after the
 //     reset has them, and serves two streams: the learner's block and the yellow team's;
 //   * ou_buf afterwards holds all twelve applied, pre-clamp actions.
-// Both observation streams of a wrapped mode are nontemporal, versus or not.
+// Every store group's cache policy comes from args.store_policy (store_policy on the host), versus or not.
 //
 // The mirror step (MIRROR, step_mirror_kernel<MODE>): both teams are learner rows.  The yellow
 // learner's action rows (yl.actions: SA slots 6..7, CMA / DMA 6..11) come in like the versus step's
@@ -995,6 +1079,7 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   stage_obs_table(tab, threadIdx.x);
 
   const int64_t n = args.n;
+  const uint32_t pol = args.store_policy;
   const int lane = threadIdx.x;
   const int fl = lane & 31;        // this lane's field within the wave
   const bool writer = lane < 32;   // writes the field's LDS record slots
@@ -1089,8 +1174,8 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   // -- terminal observation (envs/vss.py:195-196) ----------------------------------------------------------
   if (lane < kFpw) write_obs_record<MIRROR ? 6 : A>(orec, b, a);
   __syncthreads();
-  coop_store_obs<A, 0, REC>(args.io.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL);
-  if constexpr (MIRROR) coop_store_obs<A, 3, REC>(yl.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, true);
+  coop_store_obs<A, 0, REC>(args.io.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, policy_of(pol, kGrpTerminal));
+  if constexpr (MIRROR) coop_store_obs<A, 3, REC>(yl.terminal_obs + f0 * (52 * A), nv, lds, tab, lane, policy_of(pol, kGrpYellow));
   __syncthreads();
 
   // -- reset_dones (envs/vss.py:202, 267-333) ---------------------------------------------------------------
@@ -1102,16 +1187,20 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   // -- observation after reset (envs/vss.py:203); versus, mirror: the yellow team's block from the same record
   if (lane < kFpw) write_obs_record<TWO ? 6 : A>(orec, b, dof);
   __syncthreads();
-  coop_store_obs<A, 0, REC>(args.io.obs + f0 * (52 * A), nv, lds, tab, lane, MODE != VSS_MODE_FULL || args.nt_obs != 0);
-  if constexpr (VERSUS) coop_store_obs<3, 3, REC>(vs.opp_obs + f0 * (52 * 3), nv, lds, tab, lane, true);
-  if constexpr (MIRROR) coop_store_obs<A, 3, REC>(yl.obs + f0 * (52 * A), nv, lds, tab, lane, true);
+  coop_store_obs<A, 0, REC>(args.io.obs + f0 * (52 * A), nv, lds, tab, lane, policy_of(pol, kGrpObs));
+  if constexpr (VERSUS) coop_store_obs<3, 3, REC>(vs.opp_obs + f0 * (52 * 3), nv, lds, tab, lane, policy_of(pol, kGrpYellow));
+  if constexpr (MIRROR) coop_store_obs<A, 3, REC>(yl.obs + f0 * (52 * A), nv, lds, tab, lane, policy_of(pol, kGrpYellow));
   __syncthreads();
 
   // -- bookkeeping --------------------------------------------------------------------------------------------
   const uint8_t time_out = (progress >= (int64_t)args.p.max_episode_length - 1) && done != 0;
+  // the state: a full wave's as 16-B stores with the state group's policy; the plain policy and a
+  // partial last wave (its channels' ends are not the wave's to overwrite) keep one 4-B store per lane
+  const bool state_wave = policy_of(pol, kGrpState) != kStPlain && nv == kFpw;  // wave-uniform
+  if (state_wave) store_bodies_wave(args.s.state, n, f0, b, lds, lane, writer, policy_of(pol, kGrpState));
   if (owner) {
     const uint32_t ufl = (uint32_t)fl;
-    store_bodies(args.s.state, n, f0, fl, b);
+    if (!state_wave) store_bodies(args.s.state, n, f0, fl, b);
     at(args.s.progress_buf + f0, 8u * ufl) = progress;
     at(args.s.reset_buf + f0, 8u * ufl) = done;
     at(args.s.rng_counter + f0, 4u * ufl) = ctr + 1u;
@@ -1136,12 +1225,13 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   }
 
   // dof_velocity_buf (N,12) and, wrapped, the OU action buffer (zeroed for done fields)
+  const uint32_t aos = policy_of(pol, kGrpAos);
   if (writer) {
 #pragma unroll
     for (int k = 0; k < 12; ++k) rec[k] = dof[k];
   }
   __syncthreads();
-  coop_store<12>(args.s.dof_velocity_buf + f0 * 12, nv, lds, lane);
+  coop_store<12>(args.s.dof_velocity_buf + f0 * 12, nv, lds, lane, aos);
   __syncthreads();
   if constexpr (MODE != VSS_MODE_FULL) {
     if (writer) {
@@ -1149,7 +1239,7 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
       for (int k = 0; k < 12; ++k) rec[k] = done ? ou[k] * 0.0f : ou[k];
     }
     __syncthreads();
-    coop_store<12>(args.io.ou_buf + f0 * 12, nv, lds, lane);
+    coop_store<12>(args.io.ou_buf + f0 * 12, nv, lds, lane, aos);
     __syncthreads();
   }
 
@@ -1160,7 +1250,7 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
       for (int k = 0; k < 24; ++k) rec[k] = rew[k];
     }
     __syncthreads();
-    coop_store<24>(args.io.rew + f0 * 24, nv, lds, lane);
+    coop_store<24>(args.io.rew + f0 * 24, nv, lds, lane, aos);
     if (owner && args.io.reward_sum) at(args.io.reward_sum + f0, 4u * (uint32_t)fl) = ((rew[0] + rew[1]) + rew[2]) + rew[3];
   } else if constexpr (MODE == VSS_MODE_SA) {
     if (owner) {
@@ -1192,7 +1282,7 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
       for (int k = 0; k < 12; ++k) rec[k] = rew[k];
     }
     __syncthreads();
-    coop_store<12>(args.io.rew + f0 * 12, nv, lds, lane);
+    coop_store<12>(args.io.rew + f0 * 12, nv, lds, lane, aos);
     if (owner) {
 #pragma unroll
       for (int ag = 0; ag < 3; ++ag)
@@ -1206,7 +1296,7 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
         for (int k = 0; k < 12; ++k) rec[k] = rew[12 + k];
       }
       __syncthreads();
-      coop_store<12>(yl.rew + f0 * 12, nv, lds, lane);
+      coop_store<12>(yl.rew + f0 * 12, nv, lds, lane, aos);
       if (owner) {
 #pragma unroll
         for (int ag = 0; ag < 3; ++ag)
@@ -1310,13 +1400,13 @@ __global__ __launch_bounds__(kWave) void rollout_kernel(RolloutArgs args) {
     wait_loads();
     if (lane < kFpw) write_obs_record<6>(orec, b, a);
     __syncthreads();
-    coop_store_obs<6>(args.io.terminal_obs + (step_off + f0) * 312, nv, lds, tab, lane, true);  // K steps: past the cache
+    coop_store_obs<6>(args.io.terminal_obs + (step_off + f0) * 312, nv, lds, tab, lane, kStNt);  // K steps: past the cache
     __syncthreads();
     const ResetDraws rd{k0, k1, (uint32_t)f, ctr + (uint32_t)k, 0u, nullptr, (uint32_t)kMaxRejectRounds};
     reset_if_done<false>(valid, done, rd, b, a, dof);
     if (lane < kFpw) write_obs_record<6>(orec, b, dof);
     __syncthreads();
-    coop_store_obs<6>(args.io.obs + (step_off + f0) * 312, nv, lds, tab, lane, true);
+    coop_store_obs<6>(args.io.obs + (step_off + f0) * 312, nv, lds, tab, lane, kStNt);
     __syncthreads();
     if (writer) {
 #pragma unroll
@@ -1503,6 +1593,50 @@ static int check_step_io(int32_t mode, const vss_step_io* io) {
   return VSS_OK;
 }
 
+// The cache policy of every store group of a step (vss::policy_word), from the mode and the footprint.
+// `make STEP_STORE=<name>` compiles one of the candidate tables for every mode and footprint (A/B
+// builds, DESIGN.md §5.1 "the launch's end"); unset, the adopted table compiles.
+#define VSS_STORE_adopted 0
+#define VSS_STORE_present 1   // observation streams plain / nt as measured in profiles/r02_ablate_nt_obs.log
+#define VSS_STORE_obs_wt 2    // observation streams write-through, state and AoS rows plain
+#define VSS_STORE_all_wt 3    // everything write-through, the state as 16-B stores
+#define VSS_STORE_tail_wt 4   // what a launch writes last: obs, state and AoS rows write-through
+#define VSS_STORE_all_wtnt 5  // observation streams write-through + nt, state and AoS rows write-through
+#define VSS_STORE_wt_aos 6    // observation streams and AoS rows write-through, the state plain
+#ifndef VSS_STEP_STORE
+#define VSS_STEP_STORE VSS_STORE_adopted
+#endif
+static uint32_t store_policy(int32_t mode, int64_t n, bool two_sided) {
+  using namespace vss;
+  // `present`.  Wrapped modes: both streams (and the yellow blocks) nontemporal.  FULL: plain while the
+  // step's footprint (3,101 B per field) fits the 256 MiB Infinity Cache, past it `obs` nontemporal.
+  const bool full = mode == VSS_MODE_FULL;
+  const bool past_cache = full && n > (int64_t)(256ll << 20) / 3101;
+  const uint32_t term = full ? kStPlain : kStNt, obs = full && !past_cache ? kStPlain : kStNt;
+  // The adopted table (profiles/step_wt_bench.json).  While the mode's footprint (bench.py BYTES: 3,101 /
+  // 1,001 / 1,017 / 1,923 B per field; the versus and the mirror step are counted as their mode) fits the
+  // Infinity Cache: `wt_aos`, at 65,536 fields FULL 39.9 -> 36.1 us, SA 21.1 -> 20.3, CMA 20.9 -> 20.3, the
+  // versus and mirror steps 5-13 %.  Past it write-through streams lose (FULL at 131,072 fields: 77 against
+  // 73 us), so `present` stays.  The plain DMA step stays on `present` too: 28.3 -> 26.2 us in every pair,
+  // but the parent's own spread there (3.5 %) is too wide for the gain to count by the rule used.
+  static const int64_t kBytesPerField[4] = {3101, 1001, 1017, 1923};
+  const bool fits = n <= (int64_t)(256ll << 20) / kBytesPerField[mode];
+  const bool wt = fits && (mode != VSS_MODE_DMA || two_sided);
+  uint32_t w;
+  switch (VSS_STEP_STORE == VSS_STORE_adopted ? (wt ? VSS_STORE_wt_aos : VSS_STORE_present) : VSS_STEP_STORE) {
+    case VSS_STORE_obs_wt: w = policy_word(kStWt, kStWt, kStWt, kStPlain, kStPlain); break;
+    case VSS_STORE_all_wt: w = policy_word(kStWt, kStWt, kStWt, kStWt, kStWt); break;
+    case VSS_STORE_tail_wt: w = policy_word(term, kStWt, kStNt, kStWt, kStWt); break;
+    case VSS_STORE_all_wtnt: w = policy_word(kStWtNt, kStWtNt, kStWtNt, kStWt, kStWt); break;
+    case VSS_STORE_wt_aos: w = policy_word(kStWt, kStWt, kStWt, kStPlain, kStWt); break;
+    default: w = policy_word(term, obs, kStNt, kStPlain, kStPlain); break;
+  }
+  // store_bodies_wave addresses the whole state through one 32-bit offset: past 2^23 fields the
+  // state keeps its per-lane stores
+  if (n > (int64_t(1) << 23)) w &= ~(3u << kGrpState);
+  return w;
+}
+
 // The launch of a checked step: step_versus_kernel<mode> (VERSUS; `vs` given, mode wrapped),
 // step_mirror_kernel<mode> (MIRROR; `yl` given, mode wrapped) or step_kernel<mode, REPLAY>.
 template <bool REPLAY, bool VERSUS, bool MIRROR = false>
@@ -1510,10 +1644,7 @@ static int launch_step(void* stream, int64_t n, int32_t mode, const vss_params* 
                        const vss_step_io* io, const vss_replay_draws* rd, int rounds, const vss_versus_io* vs,
                        const vss_mirror_io* yl = nullptr) {
   if (n == 0) return VSS_OK;
-  // FULL: the observation stream nontemporal once the step's footprint (3,101 B per field) is past
-  // the 256 MiB Infinity Cache (coop_store_obs)
-  const uint32_t nt_obs = mode == VSS_MODE_FULL && n > (int64_t)(256ll << 20) / 3101 ? 1u : 0u;
-  vss::StepArgs args{n, *p, *st, *io, REPLAY ? *rd : vss_replay_draws{}, (uint32_t)rounds, nt_obs};
+  vss::StepArgs args{n, *p, *st, *io, REPLAY ? *rd : vss_replay_draws{}, (uint32_t)rounds, store_policy(mode, n, VERSUS || MIRROR)};
   const dim3 grid((unsigned)((n + vss::kFpw - 1) / vss::kFpw)), block(vss::kWave);
   hipStream_t s = (hipStream_t)stream;
   auto launch = [&](auto m) {
