@@ -22,7 +22,7 @@ import torch
 
 from . import _native as N
 
-VERSION = 1
+VERSION = N.SCRIPTED_VERSION
 F = np.float32
 
 # every constant of controller 1

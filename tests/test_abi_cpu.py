@@ -3,22 +3,66 @@ include/vss.h declares, and validates arguments without touching a GPU."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
 from vss_amd import _native as N
+from vss_amd import cheader
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def declared_functions():
-    src = open(N.HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:int64_t|int|const char\*)\s+(vss_\w+)\s*\(", src, flags=re.M)))
+    with open(N.HEADER) as f:
+        return sorted(cheader.parse(f.read()).functions)
+
+
+def library_symbols():
+    """The vss_* functions the built library exports, read from its ELF dynamic symbol table (`nm -D`)."""
+    out = subprocess.run(["nm", "-D", "--defined-only", N.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    return sorted(m.group(1) for m in re.finditer(r"^\S+\s+T\s+(vss_\w+)$", out, flags=re.M))
 
 
 def test_header_declares_the_expected_entry_points():
-    assert declared_functions() == sorted(N.EXPORTED)
+    """The header's prototypes are the library's exported functions, all 61 of them, each once; EXPORTED is that list."""
+    with open(N.HEADER) as f:
+        text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    names = re.findall(r"\b(vss_\w+)\s*\(", text)  # every name in front of a parenthesis, not through the parser
+    assert len(names) == len(set(names)) == 61
+    assert sorted(names) == declared_functions() == sorted(N.EXPORTED) and len(N.EXPORTED) == 61
+    lib = N.load()
+    for name in names:
+        assert hasattr(lib, name), name
+    if shutil.which("nm"):
+        assert library_symbols() == sorted(names)
+    for name in ("vss_step", "vss_step_mirror", "vss_gae", "vss_scripted_team", "vss_perceive",
+                 "vss_linear_tanh_loss_bf16x6"):
+        assert name in N.EXPORTED, name
+
+
+def test_stamped_is_the_makefiles_list():
+    """N.STAMPED is csrc/Makefile's STAMPED line, in its order: the nine kernel sources, the shared row header, the
+    ABI header and the Makefile itself."""
+    with open(os.path.join(N.CSRC, "Makefile")) as f:
+        (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
+    files = [w.split(":")[0] for w in line.split()]
+    assert list(N.STAMPED) == [os.path.normpath(os.path.join(N.CSRC, w)) for w in files]
+    assert [os.path.basename(p) for p in N.STAMPED] == [
+        "vss_step.hip", "vss_update.hip", "vss_policy.hip", "vss_gemm_x6.hip", "vss_loss.hip", "vss_optim.hip",
+        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_loss_row.h", "vss.h", "Makefile"]
+    assert N.HEADER in N.STAMPED and all(os.path.isfile(p) for p in N.STAMPED)
+    hips = sorted(f for f in os.listdir(N.CSRC) if f.endswith(".hip"))
+    assert hips == sorted(f for f in files if f.endswith(".hip"))  # no kernel source left out of the stamp
+
+
+def test_missing_stamped_line_is_an_error(tmp_path, monkeypatch):
+    os.makedirs(tmp_path / "csrc")
+    (tmp_path / "csrc" / "Makefile").write_text("all:\n")
+    monkeypatch.setattr(N, "CSRC", str(tmp_path / "csrc"))
+    with pytest.raises(N.NativeError, match="STAMPED"):
+        N._stamped()
 
 
 def test_library_loads_and_exports_every_declared_symbol():

@@ -25,6 +25,7 @@ def call(n_steps=8, n_rows=64, rewards=FAKE, values=FAKE, next_values=None, term
 def test_vss_gae_is_exported_and_the_abi_version_stays():
     assert "vss_gae" in N.EXPORTED
     assert N.load().vss_abi_version() == 2 == N.ABI_VERSION
+    assert N.STATE_CHANNELS == 58 and N.MODE_DMA == 3
 
 
 @pytest.mark.parametrize("form", [FORM_A, FORM_B])

@@ -79,7 +79,7 @@ def test_the_symbol_is_exported_and_declared_and_the_abi_version_stays():
     assert re.search(r"\bint\s+vss_scripted_team\s*\(", header)
     assert re.search(r"#define\s+VSS_SCRIPTED_VERSION\s+1\b", header)
     assert N.load().vss_abi_version() == 2 == N.ABI_VERSION
-    assert S.VERSION == 1
+    assert S.VERSION == 1 == N.SCRIPTED_VERSION
 
 
 def test_rejected_calls_and_the_zero_size_call():
