@@ -75,6 +75,9 @@ def make_env(args):
     delay, noise = perception_args(args)
     if delay or noise.any():  # --obs-delay / --obs-noise-*: with all of them zero the chain is as without the flags
         wrapped = Perceived(wrapped, delay, noise, perception_seed(getattr(args, "seed", None)))
+    params = actuation_args(args)
+    if params.any():  # --act-*: the outermost wrapper; with all of them zero the chain is as without the flags
+        wrapped = Actuated(wrapped, params, actuation_seed(getattr(args, "seed", None)))
     return envs, wrapped
 
 
@@ -101,6 +104,36 @@ def evaluation_channel(args, env, offset: int = 2):
     n = env.num_fields
     return P.PerceptionChannel(n, P.layout_full_blue(), delay, noise, perception_seed(getattr(args, "seed", None), offset),
                                env.device, rows=n * 6)
+
+
+def actuation_args(args):
+    """Params of --act-gain / -noise / -deadband / -loss / -levels; absent flags are zero."""
+    from vss_amd.actuate import Params
+    return Params(*(float(getattr(args, f"act_{k}", 0.0) or 0.0) for k in ("gain", "noise", "deadband", "loss")),
+                  int(getattr(args, "act_levels", 0) or 0))
+
+
+def actuation_seed(seed, offset: int = 0) -> int:
+    """The actuation channel's Philox key, built as perception_seed with a constant of its own; `offset` separates
+    the arena's (1) and evaluate()'s (2) channels from the training's."""
+    return (int(seed or 0) * 1000003 + int(os.environ.get("RANK", 0))) * 2654435761 + 0xAC7_0A7E + int(offset)
+
+
+def evaluation_actuation(args, env, offset: int = 2):
+    """evaluate()'s channel over the blue half of the raw env's FULL action buffer (play.play_matches), with a key of
+    its own; None when the actuation flags are all zero."""
+    from vss_amd import actuate as A
+    params = actuation_args(args)
+    if not params.any():
+        return None
+    n = env.num_fields
+    return A.ActuationChannel(n, A.layout_full_blue(), params, actuation_seed(getattr(args, "seed", None), offset),
+                              env.device, rows=n * 6)
+
+
+def evaluation_channels(args, env):
+    """evaluate()'s (perception channel, actuation channel) for play.play_matches; None for flags that are all zero."""
+    return evaluation_channel(args, env), evaluation_actuation(args, env)
 
 
 class RecordEpisodeStatisticsTorch(Wrapper):
@@ -390,6 +423,105 @@ class Perceived(Wrapper):
         self.channel.load_state_dict(entry(state, "channel", "Perceived"))
         if self.opponent_channel is not None:
             self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Perceived"))
+
+
+class _ActuatedTeam:
+    """A policy team in front of the yellow channel: what it commands passes the channel in place before the step
+    reads it; everything else (check_env, observe, state, version ...) is the team's own."""
+
+    def __init__(self, team, channel, dones):
+        self.team, self.channel, self.dones = team, channel, dones
+
+    def __call__(self, act, obs):
+        self.team(act, obs)
+        self.channel.actuate(act, self.dones, out=act)
+
+    def __getattr__(self, name):
+        if name in ("team", "channel", "dones"):  # not set yet (a copy under construction): no forwarding loop
+            raise AttributeError(name)
+        return getattr(self.team, name)
+
+
+class Actuated(Wrapper):
+    """Motor gain, command noise, quantisation, deadband and packet loss between the policy and the step
+    (vss_amd/actuate.py): step(action) takes the learner's commands through one vss_actuate launch
+    and steps the inner env with what the wheels apply.  `action` itself is not modified (the rollout keeps it for
+    the log-prob); observations, rewards, dones and infos pass through.  The outermost env wrapper: outside
+    Perceived when both are on.
+
+    A policy opponent (--opponent self, pool or a checkpoint) commands through a second channel over the versus
+    step's opp_act, in place: the same seed, call index and dones, yellow's entities -- one world.  The scripted
+    team, zero and the kernel's OU process are not actuated.  The mirror wrappers get one two-team channel."""
+
+    def __init__(self, env, params, seed: int):
+        super().__init__(env)
+        from vss_amd import actuate as A
+        base = env.env if isinstance(env, Perceived) else env  # the SA / CMA / DMA or mirror wrapper
+        vss = base.env
+        n = vss.num_fields
+        if isinstance(base, _MirrorWrapper):
+            robots = 3 if base.MODE in (N.MODE_CMA, N.MODE_DMA) else 1
+            layout, stride, dones = A.layout_mirror(robots, n), base.FIELD_ROWS, base._dones
+        else:
+            layout = A.layout_sa() if base.MODE == N.MODE_SA else A.layout_team()
+            stride = base.ROWS_PER_FIELD
+            dones = vss.reset_buf if base._dones is None else base._dones
+        self._base, self._dones_prev = base, dones  # the persistent buffer every step returns as its dones
+        self.params, self.seed = A.Params(*params), int(seed)
+        self.channel = A.ActuationChannel(n, layout, self.params, self.seed, vss.device, done_stride=stride)
+        self.opponent_channel = None
+
+    @property
+    def _opp_obs(self):
+        return self.env._opp_obs
+
+    @property
+    def _opp_act(self):
+        return self.env._opp_act
+
+    def set_opponent(self, team=None, actuated=None):
+        """The inner wrapper's set_opponent; `actuated` (default: a SnapshotOpponent or an OpponentPool, i.e. a
+        policy) puts the yellow channel behind the team."""
+        from vss_amd import actuate as A
+        from vss_amd.opponent import OpponentPool, SnapshotOpponent
+        policy = isinstance(team, (SnapshotOpponent, OpponentPool))
+        if actuated is None:
+            actuated = policy
+        perceived = {"perceived": policy} if isinstance(self.env, Perceived) else {}  # its isinstance sees the team
+        if team is None or not actuated:
+            self.env.set_opponent(team, **perceived)
+            self.opponent_channel = None
+            return
+        vss = self._base.env
+        ch = A.ActuationChannel(vss.num_fields, A.layout_opponent(), self.params, self.seed, vss.device,
+                                done_stride=self.channel.done_stride)
+        ch.start(call=self.channel.call)  # the learner's channel's next call: one world
+        self.env.set_opponent(_ActuatedTeam(team, ch, self._dones_prev), **perceived)
+        self.opponent_channel = ch
+
+    def reset(self, **kwargs):
+        obs = self.env.reset(**kwargs)
+        self.channel.start(call=0, zero=True)
+        if self.opponent_channel is not None:
+            self.opponent_channel.start(call=0, zero=True)
+        return obs
+
+    def step(self, action):
+        return self.env.step(self.channel.actuate(action, self._dones_prev))
+
+    def state_dict(self) -> dict:
+        """The inner wrapper's state and the channels' (held, gain, episode, output, call, start flag), on the CPU."""
+        out = {"inner": self.env.state_dict(), "channel": self.channel.state_dict()}
+        if self.opponent_channel is not None:
+            out["opponent_channel"] = self.opponent_channel.state_dict()
+        return out
+
+    def load_state_dict(self, state: dict) -> None:
+        from vss_amd.checkpoint import entry
+        self.env.load_state_dict(entry(state, "inner", "Actuated"))
+        self.channel.load_state_dict(entry(state, "channel", "Actuated"))
+        if self.opponent_channel is not None:
+            self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Actuated"))
 
 
 class _MirrorWrapper(Wrapper):

@@ -132,10 +132,12 @@ def baseline_teams(root="base_nets", device="cuda:0"):
 
 
 @torch.no_grad()
-def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk=32, perceive=None):
+def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk=32, perceive=None, actuate=None):
     """Mean blue goal score and episode length over the first `n_matches` finished episodes.  `perceive`: a
     vss_amd.perceive.PerceptionChannel over the blue rows of the FULL layout (layout_full_blue, rows = 6 N);
-    blue then acts on what the camera would have delivered, yellow on the truth."""
+    blue then acts on what the camera would have delivered, yellow on the truth.  `actuate`: a
+    vss_amd.actuate.ActuationChannel over the blue half of the FULL action buffer (layout_full_blue, rows = 6 N);
+    blue's commands then pass it in place, started afresh here, and yellow's stay exact."""
     envs.reset_buf[:] = 1
     envs.reset_dones()  # like the reference, obs_buf is not recomputed here (play.py:132-151)
     n = envs.num_fields
@@ -143,6 +145,9 @@ def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk
     action_buf = torch.zeros((n,) + tuple(envs.action_space.shape), device=envs.device)
     obs = envs.reset()["obs"]
     blue_obs = obs if perceive is None else perceive.start(obs)
+    dones = None
+    if actuate is not None:
+        actuate.start(call=0, zero=True)
     rec = None
     if video_path:  # play.py:134-142: the first 300 steps of field 0 (envs/render.py, GIF)
         from envs.render import FrameRecorder
@@ -154,6 +159,8 @@ def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk
         lsum = torch.zeros(chunk, device=envs.device, dtype=torch.float64)
         for t in range(chunk):
             blue_team(action_buf[:, 0], blue_obs[:, 0])
+            if actuate is not None:  # done_prev: the previous step's dones (envs.reset_buf, a persistent buffer)
+                actuate.actuate(action_buf, dones, out=action_buf)
             yellow_team(action_buf[:, 1], obs[:, 1])
             o, rew, dones, info = envs.step(action_buf)
             if rec is not None:

@@ -68,6 +68,11 @@ class Arena:
             delay, noise = perception_args(args)
             if delay or noise.any():
                 self.wrapper = Perceived(self.wrapper, delay, noise, perception_seed(args.seed, 1))
+            # --act-*: blue's commands pass a channel of the arena's own; reset() starts it afresh (state zeroed, call 0)
+            from envs.wrappers import Actuated, actuation_args, actuation_seed
+            params = actuation_args(args)
+            if params.any():
+                self.wrapper = Actuated(self.wrapper, params, actuation_seed(args.seed, 1))
             self.policy = FusedPolicy(agent, seed=int(args.seed) * 7919 + 15485863, actor_only=True)
         self.opponents = {t: (None if t == "ou" else get_team(t)) for t in self.teams}
         self.n_fields = n

@@ -1,4 +1,4 @@
-"""Build libvss_amd.so for gfx950 (hipcc cross-compiles; no GPU needed)."""
+"""Build libvss_amd.so and libvss_actuate.so for gfx950 (hipcc cross-compiles; no GPU needed)."""
 from __future__ import annotations
 
 import os
@@ -14,6 +14,7 @@ def build(arch: str = "gfx950", verbose: bool = False) -> str:
     if not verbose:
         cmd.insert(1, "-s")
     subprocess.run(cmd, check=True)
-    if not os.path.exists(out):
-        raise RuntimeError(f"build did not produce {out}")
+    for lib in (out, os.path.join(HERE, "libvss_actuate.so")):  # the second one: csrc/actuate, by the same make
+        if not os.path.exists(lib):
+            raise RuntimeError(f"build did not produce {lib}")
     return out

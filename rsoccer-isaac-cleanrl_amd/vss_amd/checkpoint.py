@@ -28,8 +28,21 @@ STRUCTURAL = ("env_id", "num_envs", "num_steps", "seed", "opponent", "opponent_p
 # the perception channel's flags (vss_amd/perceive.py): structural as well -- the ring's depth and the set of state
 # owners follow them -- and absent from a state file written before they existed, where they count as zero
 PERCEPTION_STRUCTURAL = ("obs_delay", "obs_noise_pos", "obs_noise_vel", "obs_noise_ang", "obs_noise_angvel")
+# the actuation channel's flags (vss_amd/actuate.py): structural in the same way, zero where a state file lacks them
+ACTUATION_STRUCTURAL = ("act_gain", "act_noise", "act_levels", "act_deadband", "act_loss")
 # set by train() itself or about the checkpoint, not hyper-parameters: never reported as changed
 _NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
+
+
+def add_actuation_arguments(p):
+    """The command line's actuation flags, all 0 by default: the keys of ACTUATION_STRUCTURAL (envs/wrappers.py Actuated).
+    Returns the parser."""
+    p.add_argument("--act-gain", type=float, default=0.0, help="actuation: std of the per-episode wheel gains (0..0.3)")
+    p.add_argument("--act-noise", type=float, default=0.0, help="actuation: std of the per-step noise on every applied command")
+    p.add_argument("--act-levels", type=int, default=0, help="actuation: commands are multiples of 1 / levels (127: 8 bits); 0: exact")
+    p.add_argument("--act-deadband", type=float, default=0.0, help="actuation: a received command below this does not move the wheel")
+    p.add_argument("--act-loss", type=float, default=0.0, help="actuation: a team's packet is lost with this probability per step")
+    return p
 
 
 def opponent_mode(value) -> str:
@@ -49,11 +62,11 @@ def check_compatible(saved_args, args, log=print) -> list:
     ValueError naming the key and both values; every other argument is taken from `args`, and each one that
     differs from the saved value is reported once through `log` (None: silent).  Returns the changed keys."""
     saved, new = plain_args(saved_args), plain_args(args)
-    for k in STRUCTURAL + PERCEPTION_STRUCTURAL:
+    for k in STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL:
         a, b = saved.get(k), new.get(k)
         if k == "opponent":
             a, b = opponent_mode(a), opponent_mode(b)
-        if k in PERCEPTION_STRUCTURAL:
+        if k in PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL:
             a, b = a or 0, b or 0
         if a != b:
             raise ValueError(f"--resume: {k} is structural and differs: the state file has {a!r}, this command line {b!r}")
