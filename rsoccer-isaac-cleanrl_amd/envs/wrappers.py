@@ -75,6 +75,8 @@ def make_env(args):
     delay, noise = perception_args(args)
     if delay or noise.any():  # --obs-delay / --obs-noise-*: with all of them zero the chain is as without the flags
         wrapped = Perceived(wrapped, delay, noise, perception_seed(getattr(args, "seed", None)))
+    if estimation_args(args):  # --obs-predict 1: between Perceived and the policy; with 0 the chain is as without the flag
+        wrapped = Estimated(wrapped)
     params = actuation_args(args)
     if params.any():  # --act-*: the outermost wrapper; with all of them zero the chain is as without the flags
         wrapped = Actuated(wrapped, params, actuation_seed(getattr(args, "seed", None)))
@@ -104,6 +106,28 @@ def evaluation_channel(args, env, offset: int = 2):
     n = env.num_fields
     return P.PerceptionChannel(n, P.layout_full_blue(), delay, noise, perception_seed(getattr(args, "seed", None), offset),
                                env.device, rows=n * 6)
+
+
+def estimation_args(args) -> bool:
+    """--obs-predict as a bool; an absent flag is 0.  1 with --obs-delay 0 is refused (checkpoint.check_estimation)."""
+    from vss_amd.checkpoint import check_estimation
+    return bool(int(getattr(check_estimation(args), "obs_predict", 0) or 0))
+
+
+def evaluation_estimation(args, env):
+    """evaluate()'s estimation channel over the blue rows of the raw env's FULL layout (play.play_matches), applied
+    after the perception channel; None when --obs-predict is 0."""
+    from vss_amd import estimate as E
+    if not estimation_args(args):
+        return None
+    n = env.num_fields
+    return E.EstimationChannel(n, E.layout_full_blue(), perception_args(args)[0], env.device, rows=n * 6)
+
+
+def evaluation_kwargs(args, env) -> dict:
+    """evaluate()'s channels as play.play_matches' keyword arguments; None for flags that are all zero."""
+    perceive, actuate = evaluation_channels(args, env)
+    return dict(perceive=perceive, actuate=actuate, estimate=evaluation_estimation(args, env))
 
 
 def actuation_args(args):
@@ -425,6 +449,106 @@ class Perceived(Wrapper):
             self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Perceived"))
 
 
+class _EstimatedTeam:
+    """A policy team behind the yellow estimation channel: it acts on the estimated opponent rows, whatever rows it
+    is handed; everything else (check_env, observe, state, version ...) is the team's own."""
+
+    def __init__(self, team, channel):
+        self.team, self.channel = team, channel
+
+    def __call__(self, act, obs):
+        self.team(act, self.channel.obs_out.view(obs.shape))
+
+    def __getattr__(self, name):
+        if name in ("team", "channel"):  # not set yet (a copy under construction): no forwarding loop
+            raise AttributeError(name)
+        return getattr(self.team, name)
+
+
+class Estimated(Wrapper):
+    """Dead reckoning round `Perceived` (vss_amd/estimate.py): `obs` and info["terminal_observation"]
+    become the perceived rows rolled forward to the present -- by the rows' age, with the project's own drive model
+    and the commands given in the meantime -- by one vss_estimate launch per step.  Rewards, dones and every other
+    info pass through.  It goes round Perceived and inside Actuated.
+
+    Where Perceived puts a second channel in front of a policy opponent, a second estimation channel goes behind
+    it: it estimates Perceived's opponent_channel.obs_out with the opponent layout, the same call index and the same
+    dones, and the team acts on its output.  The mirror wrappers get one two-team channel."""
+
+    def __init__(self, env):
+        if not isinstance(env, Perceived) or env.delay < 1:
+            raise ValueError("Estimated goes round a Perceived wrapper with a delay of at least 1: without latency there "
+                             "is nothing to predict")
+        super().__init__(env)
+        from vss_amd import estimate as E
+        self._base = env.env  # the SA / CMA / DMA or mirror wrapper
+        vss = self._base.env
+        self.delay = env.delay
+        self.channel = E.EstimationChannel(vss.num_fields, E.of_perception(env.channel.layout), self.delay, vss.device,
+                                           done_stride=env.channel.done_stride)
+        self.opponent_channel = None
+        self.channel.start(env.channel.obs_out.view(self._base._obs.shape))  # as Perceived's constructor starts its own
+
+    @property
+    def _opp_obs(self):
+        return self.env._opp_obs
+
+    @property
+    def _opp_act(self):
+        return self.env._opp_act
+
+    def _perceived_opponent_rows(self):
+        return self.env.opponent_channel.obs_out.view(self.env._opp_obs.shape)
+
+    def set_opponent(self, team=None, perceived=None):
+        """Perceived's set_opponent; where that puts the yellow perception channel in front of the team (`perceived`,
+        default: a SnapshotOpponent or an OpponentPool), the yellow estimation channel goes behind it."""
+        from vss_amd import estimate as E
+        from vss_amd.opponent import OpponentPool, SnapshotOpponent
+        if perceived is None:
+            perceived = isinstance(team, (SnapshotOpponent, OpponentPool))
+        if team is None or not perceived:
+            self.env.set_opponent(team, perceived=False)
+            self.opponent_channel = None
+            return
+        vss = self._base.env
+        ch = E.EstimationChannel(vss.num_fields, E.layout_opponent(), self.delay, vss.device,
+                                 done_stride=self.channel.done_stride)
+        self.env.set_opponent(_EstimatedTeam(team, ch), perceived=True)
+        self.opponent_channel = ch
+        ch.start(self._perceived_opponent_rows(), call=max(self.channel.call - 1, 0))  # the learner's rows' last call
+
+    def reset(self, **kwargs):
+        obs = self.env.reset(**kwargs)["obs"]
+        if self.opponent_channel is not None:
+            self.opponent_channel.start(self._perceived_opponent_rows())
+        return {"obs": self.channel.start(obs)}
+
+    def step(self, action):
+        obs, reward, dones, infos = self.env.step(action)
+        e_obs, e_term = self.channel.estimate(obs["obs"], infos["terminal_observation"], dones)
+        if self.opponent_channel is not None:
+            # no terminal row on the yellow side: the perceived rows stand in and the second output is not used
+            rows = self._perceived_opponent_rows()
+            self.opponent_channel.estimate(rows, rows, dones)
+        infos = dict(infos, terminal_observation=e_term)
+        return {"obs": e_obs}, reward, dones, infos
+
+    def state_dict(self) -> dict:
+        """The inner wrappers' state and the channels' (ring, age, outputs, call), on the CPU."""
+        out = {"inner": self.env.state_dict(), "channel": self.channel.state_dict()}
+        if self.opponent_channel is not None:
+            out["opponent_channel"] = self.opponent_channel.state_dict()
+        return out
+
+    def load_state_dict(self, state: dict) -> None:
+        from vss_amd.checkpoint import entry
+        self.env.load_state_dict(entry(state, "inner", "Estimated"))
+        self.channel.load_state_dict(entry(state, "channel", "Estimated"))
+        if self.opponent_channel is not None:
+            self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Estimated"))
+
+
 class _ActuatedTeam:
     """A policy team in front of the yellow channel: what it commands passes the channel in place before the step
     reads it; everything else (check_env, observe, state, version ...) is the team's own."""
@@ -456,7 +580,9 @@ class Actuated(Wrapper):
     def __init__(self, env, params, seed: int):
         super().__init__(env)
         from vss_amd import actuate as A
-        base = env.env if isinstance(env, Perceived) else env  # the SA / CMA / DMA or mirror wrapper
+        base = env
+        while isinstance(base, (Perceived, Estimated)):  # down to the SA / CMA / DMA or mirror wrapper
+            base = base.env
         vss = base.env
         n = vss.num_fields
         if isinstance(base, _MirrorWrapper):
@@ -487,7 +613,7 @@ class Actuated(Wrapper):
         policy = isinstance(team, (SnapshotOpponent, OpponentPool))
         if actuated is None:
             actuated = policy
-        perceived = {"perceived": policy} if isinstance(self.env, Perceived) else {}  # its isinstance sees the team
+        perceived = {"perceived": policy} if isinstance(self.env, (Perceived, Estimated)) else {}  # its isinstance sees the team
         if team is None or not actuated:
             self.env.set_opponent(team, **perceived)
             self.opponent_channel = None

@@ -29,8 +29,8 @@ the loop -- and the machinery under it lives in vss_amd/:
   learner rows, two per field (dma: six);
 * `--opponent scripted` (a build addition): the yellow team is the scripted benchmark team (vss_amd/scripted.py,
   one vss_scripted_team launch per step) -- a fixed opponent that plays, with nothing to snapshot or sync;
-* `--obs-delay D --obs-noise-pos|vel|ang|angvel S`, `--act-gain|noise|levels|deadband|loss X` (build additions): rows D steps
-  late with pose noise (vss_amd/perceive.py), commands through imperfect motors and radio (vss_amd/actuate.py); zero: off;
+* `--obs-delay D --obs-noise-*`, `--obs-predict 1`, `--act-*` (build additions): rows D steps late with pose noise
+  (perceive.py), rolled forward to the present (estimate.py), commands through imperfect motors (actuate.py); 0: off;
 * `--eval-every K` (a build addition): every K-th update rank 0 plays the live agent against fixed teams on a
   separate arena env (vss_amd/arena.py) and adds the scores to the update's record; the training's bits do not move.
 """
@@ -155,7 +155,7 @@ def parse_args(argv=None):
         p.add_argument(f"--obs-noise-{k}", type=float, default=0.0, help=f"vision noise: std of every {what}; 0: none")
     p.add_argument("--checkpoint-every", type=int, default=0, help="every K-th update: <run>-state.pt, <run>-agent-u<update>.pt")
     p.add_argument("--resume", type=str, default=None, help="a <run>-state.pt: go on after its update, bit-equal (DESIGN.md §15)")
-    args = CK.add_actuation_arguments(p).parse_args(argv)  # + --act-gain / -noise / -levels / -deadband / -loss (Actuated)
+    args = CK.check_estimation(CK.add_channel_arguments(p).parse_args(argv))  # + --act-* (Actuated), --obs-predict (Estimated)
     args.batch_size = int(args.num_envs * args.num_steps)
     args.minibatch_size = int(args.batch_size // args.num_minibatches)
     return args
@@ -349,9 +349,9 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
     the reference's Validation/* names and are returned.  The scripted team (a build addition) is played and
     reported too, as Validation/Score/scripted and Validation/Length/scripted, outside Score Mean / Length
     Mean: those stay over the reference's teams."""
-    from envs.wrappers import evaluation_channels
+    from envs.wrappers import evaluation_kwargs
     from play import baseline_teams, get_team, play_matches
-    perceive, actuate = evaluation_channels(args, unwrapped_env)  # --obs-* / --act-*: blue as in training; else None
+    channels = evaluation_kwargs(args, unwrapped_env)  # --obs-* / --act-* / --obs-predict: blue as in training; else None
     unwrapped_env.w_goal, unwrapped_env.w_grad, unwrapped_env.w_move, unwrapped_env.w_energy = 1.0, 0.0, 0.0, 0.0
     device = unwrapped_env.device
     teams = baseline_teams(device=str(device))
@@ -364,7 +364,7 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
         for team, seeds in teams.items():
             t_score = t_len = 0.0
             for seed, yellow in seeds.items():
-                r, ln = play_matches(unwrapped_env, blue, yellow, args.eval_matches, perceive=perceive, actuate=actuate)
+                r, ln = play_matches(unwrapped_env, blue, yellow, args.eval_matches, **channels)
                 t_score += r
                 t_len += ln
                 scores.append(r)
@@ -374,7 +374,7 @@ def evaluate(args, unwrapped_env, checkpoint: str, writer, global_step: int) -> 
         res["Validation/Score Mean"] = sum(scores) / len(scores)
         res["Validation/Length Mean"] = sum(lengths) / len(lengths)
         res["Validation/Score/scripted"], res["Validation/Length/scripted"] = play_matches(
-            unwrapped_env, blue, get_team("scripted"), args.eval_matches, perceive=perceive, actuate=actuate)
+            unwrapped_env, blue, get_team("scripted"), args.eval_matches, **channels)
         for k, v in res.items():
             writer.add_scalar(f"{algo}/{k}", v, global_step)
         print(f"evaluation {algo}: " + ", ".join(f"{k} {v:.3f}" for k, v in res.items()), flush=True)

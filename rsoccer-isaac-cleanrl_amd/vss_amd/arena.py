@@ -68,6 +68,10 @@ class Arena:
             delay, noise = perception_args(args)
             if delay or noise.any():
                 self.wrapper = Perceived(self.wrapper, delay, noise, perception_seed(args.seed, 1))
+            # --obs-predict 1: the perceived rows rolled forward, as in training; reset() starts the channel afresh
+            from envs.wrappers import Estimated, estimation_args
+            if estimation_args(args):
+                self.wrapper = Estimated(self.wrapper)
             # --act-*: blue's commands pass a channel of the arena's own; reset() starts it afresh (state zeroed, call 0)
             from envs.wrappers import Actuated, actuation_args, actuation_seed
             params = actuation_args(args)

@@ -1,4 +1,4 @@
-"""Build libvss_amd.so and libvss_actuate.so for gfx950 (hipcc cross-compiles; no GPU needed)."""
+"""Build libvss_amd.so, libvss_actuate.so and libvss_estimate.so for gfx950 (hipcc cross-compiles; no GPU needed)."""
 from __future__ import annotations
 
 import os
@@ -14,7 +14,8 @@ def build(arch: str = "gfx950", verbose: bool = False) -> str:
     if not verbose:
         cmd.insert(1, "-s")
     subprocess.run(cmd, check=True)
-    for lib in (out, os.path.join(HERE, "libvss_actuate.so")):  # the second one: csrc/actuate, by the same make
+    # the second and the third one: csrc/actuate and csrc/estimate, by the same make
+    for lib in (out, os.path.join(HERE, "libvss_actuate.so"), os.path.join(HERE, "libvss_estimate.so")):
         if not os.path.exists(lib):
             raise RuntimeError(f"build did not produce {lib}")
     return out

@@ -30,6 +30,8 @@ STRUCTURAL = ("env_id", "num_envs", "num_steps", "seed", "opponent", "opponent_p
 PERCEPTION_STRUCTURAL = ("obs_delay", "obs_noise_pos", "obs_noise_vel", "obs_noise_ang", "obs_noise_angvel")
 # the actuation channel's flags (vss_amd/actuate.py): structural in the same way, zero where a state file lacks them
 ACTUATION_STRUCTURAL = ("act_gain", "act_noise", "act_levels", "act_deadband", "act_loss")
+# the estimation channel's flag (vss_amd/estimate.py): structural in the same way, 0 where a state file lacks it
+ESTIMATION_STRUCTURAL = ("obs_predict",)
 # set by train() itself or about the checkpoint, not hyper-parameters: never reported as changed
 _NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
 
@@ -43,6 +45,30 @@ def add_actuation_arguments(p):
     p.add_argument("--act-deadband", type=float, default=0.0, help="actuation: a received command below this does not move the wheel")
     p.add_argument("--act-loss", type=float, default=0.0, help="actuation: a team's packet is lost with this probability per step")
     return p
+
+
+def add_estimation_arguments(p):
+    """The command line's estimation flag, 0 by default: the key of ESTIMATION_STRUCTURAL (envs/wrappers.py Estimated).
+    Returns the parser."""
+    p.add_argument("--obs-predict", type=int, default=0, choices=(0, 1),
+                   help="1: roll the delayed rows of --obs-delay forward to the present with the drive model (Estimated)")
+    return p
+
+
+def add_channel_arguments(p):
+    """The actuation and the estimation flags.  Returns the parser."""
+    return add_estimation_arguments(add_actuation_arguments(p))
+
+
+def check_estimation(args):
+    """Refuse --obs-predict 1 without latency.  Returns args."""
+    predict = int(getattr(args, "obs_predict", 0) or 0)
+    if predict not in (0, 1):
+        raise ValueError(f"--obs-predict must be 0 or 1, got {predict}")
+    if predict and int(getattr(args, "obs_delay", 0) or 0) < 1:
+        raise ValueError("--obs-predict 1 needs --obs-delay of at least 1: the predictor rolls a delayed observation "
+                         "forward by its age, and with --obs-delay 0 every row is current, so there is nothing to predict")
+    return args
 
 
 def opponent_mode(value) -> str:
@@ -62,11 +88,11 @@ def check_compatible(saved_args, args, log=print) -> list:
     ValueError naming the key and both values; every other argument is taken from `args`, and each one that
     differs from the saved value is reported once through `log` (None: silent).  Returns the changed keys."""
     saved, new = plain_args(saved_args), plain_args(args)
-    for k in STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL:
+    for k in STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL:
         a, b = saved.get(k), new.get(k)
         if k == "opponent":
             a, b = opponent_mode(a), opponent_mode(b)
-        if k in PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL:
+        if k in PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL:
             a, b = a or 0, b or 0
         if a != b:
             raise ValueError(f"--resume: {k} is structural and differs: the state file has {a!r}, this command line {b!r}")
