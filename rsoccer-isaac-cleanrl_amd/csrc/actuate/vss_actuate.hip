@@ -5,8 +5,8 @@
 // noise.  vss_amd/actuate.py reference_actuate is the specification -- float32, one operation per line -- and this
 // file follows it line by line: + - * /, rintf, sqrtf, comparisons, selects and integer operations only, all
 // correctly rounded, denormals kept, no FMA contraction (-ffp-contract=off and the pragma below).  The Philox
-// block, u01 / u01_open0, sincos_poly / sincos_turn, logf_poly and box_muller restate vss_perceive.hip's (and so
-// vss_step.hip's).  The result equals the reference bit for bit (tests/test_actuate_gpu.py, closed loop included).
+// block, u01 and the unit box_muller are ../vss_numerics.h's, shared with vss_perceive.hip and vss_step.hip.  The
+// result equals the reference bit for bit (tests/test_actuate_gpu.py, closed loop included).
 //
 //   one field per lane: the lane loops over its n_teams * robots commands with 8-byte loads and stores.  The
 //   field's draws are therefore computed once (the perception channel computes them up to six times), episode[f]
@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../../include/vss_actuate.h"
+#include "../vss_numerics.h"
 
 #pragma clang fp contract(off)
 
@@ -34,69 +35,13 @@
 
 namespace vact {
 
+using namespace vnum;
+using namespace vnum::host;
+
 constexpr int kBlock = 256;              // fields per workgroup (four waves)
 constexpr uint32_t kPurposeStep = 8u;    // the Philox counter's purpose byte: per-step draws (noise, loss)
 constexpr uint32_t kPurposeEpisode = 9u;  // per-episode draws (gains); 0..6 are the step's, 7 perception's
 constexpr uint32_t kLossBlock = 3u;
-
-// ---- restated from vss_perceive.hip / vss_step.hip: the same operations in the same order -------------------
-__device__ __forceinline__ void philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                       uint32_t out[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604645e-08f; }
-__device__ __forceinline__ float u01_open0(uint32_t x) { return (float)((x >> 8) + 1u) * 5.9604645e-08f; }
-
-__device__ __forceinline__ void sincos_poly(float r, float& s, float& c) {
-  float r2 = r * r;
-  s = r + r * r2 * (-0.16666667f + r2 * (0.008333334f + r2 * (-1.9841270e-4f + r2 * 2.7557319e-6f)));
-  c = 1.0f + r2 * (-0.5f + r2 * (0.041666668f + r2 * (-1.3888889e-3f + r2 * (2.4801587e-5f + r2 * (-2.7557319e-7f)))));
-}
-
-__device__ __forceinline__ void sincos_turn(float u, float& s, float& c) {
-  float v = u * 4.0f;
-  int q = (int)v;
-  float t = v - (float)q;
-  float r = (t - 0.5f) * 1.5707964f;
-  float sr, cr;
-  sincos_poly(r, sr, cr);
-  float cp = (cr - sr) * 0.70710677f;
-  float sp = (cr + sr) * 0.70710677f;
-  if (q == 0) { c = cp; s = sp; }
-  else if (q == 1) { c = -sp; s = cp; }
-  else if (q == 2) { c = -cp; s = -sp; }
-  else { c = sp; s = -cp; }
-}
-
-__device__ __forceinline__ float logf_poly(float x) {
-  uint32_t u = __float_as_uint(x);
-  int e = (int)((u >> 23) & 0xffu) - 127;
-  float m = __uint_as_float((u & 0x7fffffu) | 0x3f800000u);
-  if (m > 1.4142135f) { m = m * 0.5f; e = e + 1; }
-  float s = (m - 1.0f) / (m + 1.0f);
-  float s2 = s * s;
-  float p = 2.0f + s2 * (0.6666667f + s2 * (0.4f + s2 * (0.2857143f + s2 * (0.22222222f + s2 * 0.18181819f))));
-  return (float)e * 0.69314718f + s * p;
-}
-
-__device__ __forceinline__ void box_muller(uint32_t w1, uint32_t w2, float& zc, float& zs) {
-  const float u1 = u01_open0(w1), u2 = u01(w2);
-  const float rad = sqrtf(-2.0f * logf_poly(u1));
-  float sz, cz;
-  sincos_turn(u2, sz, cz);
-  zc = rad * cz;
-  zs = rad * sz;
-}
 
 struct Args {
   int64_t n_fields, field_stride, team_stride, done_stride;
@@ -232,16 +177,6 @@ __global__ __launch_bounds__(kBlock) void actuate_kernel(const Args a) {
     out[at[j]] = make_float2(l.o, r.o);
   }
   a.episode[f] = ep;
-}
-
-inline bool misaligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
-
-// [p, p + bytes) and [q, q + bytes2) share a byte (a null pointer overlaps nothing)
-inline bool overlap(const void* p, uint64_t bytes, const void* q, uint64_t bytes2) {
-  if (!p || !q) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  if (a == b) return true;
-  return a < b ? b - a < bytes : a - b < bytes2;
 }
 
 }  // namespace vact

@@ -6,8 +6,8 @@
 // which it keeps in a ring of its own.  vss_amd/estimate.py reference_estimate is the specification -- float32, one
 // operation per line -- and this file follows it line by line: + - * /, comparisons, selects and integer operations
 // only, all correctly rounded, denormals kept, no FMA contraction (-ffp-contract=off and the pragma below).  The
-// drive lines are those of oracle/vss_oracle.c physics_field with (c, s) taken from the row; sincos_poly and
-// sincos_small restate vss_perceive.hip's (and so vss_step.hip's).  The result equals the reference bit for bit
+// drive lines are those of oracle/vss_oracle.c physics_field with (c, s) taken from the row; sincos_small is
+// ../vss_numerics.h's, shared with vss_perceive.hip and vss_step.hip.  The result equals the reference bit for bit
 // (tests/test_estimate_gpu.py, closed loop included).
 //
 //   one row per lane.  age and hist are per row, so a lane reads and writes only its own state: no lane depends on
@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "../../../include/vss_estimate.h"
+#include "../vss_numerics.h"
 
 #pragma clang fp contract(off)
 
@@ -41,33 +42,13 @@
 
 namespace vest {
 
+using namespace vnum;
+using namespace vnum::host;
+
 constexpr int kBlock = 256;  // rows per workgroup (four waves)
 constexpr int kObs = 52;     // floats per row
 constexpr int kQuads = 13;   // 16-B pieces per row
 constexpr int kNsub = 2;     // substeps per control step
-
-// ---- restated from vss_perceive.hip / vss_step.hip: the same operations in the same order -------------------
-__device__ __forceinline__ void sincos_poly(float r, float& s, float& c) {
-  float r2 = r * r;
-  s = r + r * r2 * (-0.16666667f + r2 * (0.008333334f + r2 * (-1.9841270e-4f + r2 * 2.7557319e-6f)));
-  c = 1.0f + r2 * (-0.5f + r2 * (0.041666668f + r2 * (-1.3888889e-3f + r2 * (2.4801587e-5f + r2 * (-2.7557319e-7f)))));
-}
-
-__device__ __forceinline__ void sincos_small(float x, float& s, float& c) {
-  if (fabsf(x) < 0.78f) {
-    sincos_poly(x, s, c);
-    return;
-  }
-  int k = (int)(x * 0.63661977f + (x >= 0.0f ? 0.5f : -0.5f));
-  float kf = (float)k;
-  float r = (x - kf * 1.5707964f) - kf * (-4.3711390e-8f);
-  float sr, cr;
-  sincos_poly(r, sr, cr);
-  if (k == 0) { s = sr; c = cr; }
-  else if (k == 1) { s = cr; c = -sr; }
-  else if (k == -1) { s = -cr; c = sr; }
-  else { s = -sr; c = -cr; }
-}
 
 struct Args {
   int64_t rows;  // n_teams * n_fields * robots: one lane each
@@ -239,16 +220,6 @@ __global__ __launch_bounds__(kBlock) void estimate_kernel(const Args a) {
     e[0] = own0; e[1] = own1; e[2] = own2;
   }
   a.age[p] = age_new;
-}
-
-inline bool misaligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
-
-// [p, p + bytes) and [q, q + bytes2) share a byte (a null pointer overlaps nothing)
-inline bool overlap(const void* p, uint64_t bytes, const void* q, uint64_t bytes2) {
-  if (!p || !q) return false;
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  if (a == b) return true;
-  return a < b ? b - a < bytes : a - b < bytes2;
 }
 
 template <int ROBOTS>

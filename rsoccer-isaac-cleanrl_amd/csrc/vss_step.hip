@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "../../include/vss.h"
+#include "vss_numerics.h"
 
 #pragma clang fp contract(off)
 
@@ -34,6 +35,8 @@
 #endif
 
 namespace vss {
+
+using namespace vnum;
 
 constexpr int kWave = 64;
 // Fields per step/rollout wave (one wave per workgroup; all 64 lanes take part in the streams).
@@ -136,74 +139,9 @@ __device__ __forceinline__ void stage_obs_table(uint32_t* tab, int lane) {
 }
 
 // ---- math (transcendental-free; identical op sequence in oracle/vss_oracle.c) ----------------
+// philox, u01 / u01_open0, sincos_poly / sincos_small / sincos_turn and logf_poly: vss_numerics.h, shared with the
+// three channels
 __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-
-__device__ __forceinline__ void philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2,
-                                       uint32_t c3, uint32_t out[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    // one 32 x 32 -> 64-bit product each (v_mad_u64_u32) instead of separate mul_hi / mul_lo
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ float u01(uint32_t x) { return (float)(x >> 8) * 5.9604645e-08f; }
-__device__ __forceinline__ float u01_open0(uint32_t x) { return (float)((x >> 8) + 1u) * 5.9604645e-08f; }
-
-__device__ __forceinline__ void sincos_poly(float r, float& s, float& c) {
-  float r2 = r * r;
-  s = r + r * r2 * (-0.16666667f + r2 * (0.008333334f + r2 * (-1.9841270e-4f + r2 * 2.7557319e-6f)));
-  c = 1.0f + r2 * (-0.5f + r2 * (0.041666668f + r2 * (-1.3888889e-3f + r2 * (2.4801587e-5f + r2 * (-2.7557319e-7f)))));
-}
-
-__device__ __forceinline__ void sincos_small(float x, float& s, float& c) {
-  if (fabsf(x) < 0.78f) {  // |x| < pi/4: no reduction (always the case for yaw steps)
-    sincos_poly(x, s, c);
-    return;
-  }
-  int k = (int)(x * 0.63661977f + (x >= 0.0f ? 0.5f : -0.5f));
-  float kf = (float)k;
-  float r = (x - kf * 1.5707964f) - kf * (-4.3711390e-8f);
-  float sr, cr;
-  sincos_poly(r, sr, cr);
-  if (k == 0) { s = sr; c = cr; }
-  else if (k == 1) { s = cr; c = -sr; }
-  else if (k == -1) { s = -cr; c = sr; }
-  else { s = -sr; c = -cr; }
-}
-
-__device__ __forceinline__ void sincos_turn(float u, float& s, float& c) {
-  float v = u * 4.0f;
-  int q = (int)v;
-  float t = v - (float)q;
-  float r = (t - 0.5f) * 1.5707964f;
-  float sr, cr;
-  sincos_poly(r, sr, cr);
-  float cp = (cr - sr) * 0.70710677f;
-  float sp = (cr + sr) * 0.70710677f;
-  if (q == 0) { c = cp; s = sp; }
-  else if (q == 1) { c = -sp; s = cp; }
-  else if (q == 2) { c = -cp; s = -sp; }
-  else { c = sp; s = -cp; }
-}
-
-__device__ __forceinline__ float logf_poly(float x) {
-  uint32_t u = __float_as_uint(x);
-  int e = (int)((u >> 23) & 0xffu) - 127;
-  float m = __uint_as_float((u & 0x7fffffu) | 0x3f800000u);
-  if (m > 1.4142135f) { m = m * 0.5f; e = e + 1; }
-  float s = (m - 1.0f) / (m + 1.0f);
-  float s2 = s * s;
-  float p = 2.0f + s2 * (0.6666667f + s2 * (0.4f + s2 * (0.2857143f + s2 * (0.22222222f + s2 * 0.18181819f))));
-  return (float)e * 0.69314718f + s * p;
-}
-
 
 // ---- per-field body state in registers ---------------------------------------------------------
 struct Bodies {
@@ -918,7 +856,7 @@ __device__ __forceinline__ void stage_lrn(const float2 pre[2], int nv, float* ld
 // block 2; CMA/DMA (slots 6-11: 1.h1, 2.h0, 2.h1): the lower half block 1, the upper block 2.  The
 // same operations per pair as the unsplit loop in step_kernel (bit-identical results), about a
 // third fewer VALU instructions per wave.
-__device__ __forceinline__ void box_muller(uint32_t w1, uint32_t w2, float& zc, float& zs) {
+__device__ __forceinline__ void box_muller_ou(uint32_t w1, uint32_t w2, float& zc, float& zs) {
   const float u1 = u01_open0(w1), u2 = u01(w2);
   const float rad = sqrtf(-2.0f * logf_poly(u1));
   float sz, cz;
@@ -936,9 +874,9 @@ __device__ __forceinline__ void ou_noise_split(float a[12], uint32_t k0, uint32_
     philox(k0, k1, field, ctr, kPurposeOU << 24, up ? 2u : 0u, p);
     philox(k0, k1, field, ctr, kPurposeOU << 24, up ? 2u : 1u, q);
     float c0, s0, c1, s1, c2, s2;
-    box_muller(up ? p[0] : p[2], up ? p[1] : p[3], c0, s0);  // lower: slots 2,3   upper: 8,9
-    box_muller(up ? p[2] : q[0], up ? p[3] : q[1], c1, s1);  // lower: slots 4,5   upper: 10,11
-    box_muller(q[2], q[3], c2, s2);                          // lower: slots 6,7   (upper: unused)
+    box_muller_ou(up ? p[0] : p[2], up ? p[1] : p[3], c0, s0);  // lower: slots 2,3   upper: 8,9
+    box_muller_ou(up ? p[2] : q[0], up ? p[3] : q[1], c1, s1);  // lower: slots 4,5   upper: 10,11
+    box_muller_ou(q[2], q[3], c2, s2);                          // lower: slots 6,7   (upper: unused)
     exch(c0, z[2], z[8]);
     exch(s0, z[3], z[9]);
     exch(c1, z[4], z[10]);
@@ -950,8 +888,8 @@ __device__ __forceinline__ void ou_noise_split(float a[12], uint32_t k0, uint32_
     uint32_t p[4];
     philox(k0, k1, field, ctr, kPurposeOU << 24, up ? 2u : 1u, p);
     float c0, s0, c1, s1;
-    box_muller(up ? p[0] : p[2], up ? p[1] : p[3], c0, s0);  // lower: slots 6,7   upper: 8,9
-    box_muller(p[2], p[3], c1, s1);                          // (lower: unused)    upper: 10,11
+    box_muller_ou(up ? p[0] : p[2], up ? p[1] : p[3], c0, s0);  // lower: slots 6,7   upper: 8,9
+    box_muller_ou(p[2], p[3], c1, s1);                          // (lower: unused)    upper: 10,11
     exch(c0, z[6], z[8]);
     exch(s0, z[7], z[9]);
     float unused;
@@ -972,7 +910,7 @@ __device__ __forceinline__ void ou_noise_blue_sa(float a[12], uint32_t k0, uint3
   uint32_t w[4];
   philox(k0, k1, field, ctr, kPurposeOU << 24, up ? 1u : 0u, w);
   float zc, zs, z[6];
-  box_muller(up ? w[0] : w[2], up ? w[1] : w[3], zc, zs);  // lower: slots 2,3   upper: 4,5
+  box_muller_ou(up ? w[0] : w[2], up ? w[1] : w[3], zc, zs);  // lower: slots 2,3   upper: 4,5
   exch(zc, z[2], z[4]);
   exch(zs, z[3], z[5]);
 #pragma unroll

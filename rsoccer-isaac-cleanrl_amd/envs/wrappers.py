@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from vss_amd import _native as N
-from vss_amd.checkpoint import copy_entries, to_cpu
+from vss_amd.checkpoint import copy_entries, entry, to_cpu
 
 from ._gym import Box, Wrapper
 from .vss import VSS, default_cfg
@@ -350,23 +350,57 @@ class DMA(_FusedWrapper):
         self._observation_space = Box(-np.inf, np.inf, (env.num_obs,))
 
 
-class _PerceivedTeam:
-    """A policy team behind the yellow channel: it acts on the perceived opponent rows, whatever rows the
-    step hands it; everything else (check_env, observe, state, version ...) is the team's own."""
+class _ChannelTeam:
+    """A policy team with a yellow channel in front of or behind it: a subclass's __call__ takes the team through
+    the channel; everything else (check_env, observe, state, version ...) is the team's own."""
+    _own = ("team", "channel")
 
     def __init__(self, team, channel):
         self.team, self.channel = team, channel
 
-    def __call__(self, act, obs):
-        self.team(act, self.channel.obs_out.view(obs.shape))
-
     def __getattr__(self, name):
-        if name in ("team", "channel"):  # not set yet (a copy under construction): no forwarding loop
+        if name in self._own:  # not set yet (a copy under construction): no forwarding loop
             raise AttributeError(name)
         return getattr(self.team, name)
 
 
-class Perceived(Wrapper):
+class _ChannelWrapper(Wrapper):
+    """What Perceived, Estimated and Actuated share: a `channel` over the learner's rows or commands, an
+    `opponent_channel` (or None) over a policy opponent's, the inner wrapper's opponent buffers, and the checkpoint
+    entries, labelled with the class's name."""
+
+    @property
+    def _opp_obs(self):
+        return self.env._opp_obs
+
+    @property
+    def _opp_act(self):
+        return self.env._opp_act
+
+    def state_dict(self) -> dict:
+        """The inner wrappers' state and the channels' (their device tensors and call counters), on the CPU."""
+        out = {"inner": self.env.state_dict(), "channel": self.channel.state_dict()}
+        if self.opponent_channel is not None:
+            out["opponent_channel"] = self.opponent_channel.state_dict()
+        return out
+
+    def load_state_dict(self, state: dict) -> None:
+        label = type(self).__name__
+        self.env.load_state_dict(entry(state, "inner", label))
+        self.channel.load_state_dict(entry(state, "channel", label))
+        if self.opponent_channel is not None:
+            self.opponent_channel.load_state_dict(entry(state, "opponent_channel", label))
+
+
+class _PerceivedTeam(_ChannelTeam):
+    """Behind the yellow perception channel: the team acts on the perceived opponent rows, whatever rows the step
+    hands it."""
+
+    def __call__(self, act, obs):
+        self.team(act, self.channel.obs_out.view(obs.shape))
+
+
+class Perceived(_ChannelWrapper):
     """Observation latency and vision noise round an SA / CMA / DMA or mirror wrapper (vss_amd/perceive.py,
     DESIGN.md §17): `obs` and info["terminal_observation"] become what an overhead camera would have delivered --
     `delay` steps late, Gaussian noise on every pose -- by one vss_perceive launch per step.  Rewards, dones and
@@ -392,14 +426,6 @@ class Perceived(Wrapper):
         self.channel = P.PerceptionChannel(n, layout, self.delay, self.noise, self.seed, vss.device, done_stride=stride)
         self.opponent_channel = None
         self.channel.start(env._obs)  # as the inner wrapper's constructor computes its first observation
-
-    @property
-    def _opp_obs(self):
-        return self.env._opp_obs
-
-    @property
-    def _opp_act(self):
-        return self.env._opp_act
 
     def set_opponent(self, team=None, perceived=None):
         """The inner wrapper's set_opponent; `perceived` (default: a SnapshotOpponent or an OpponentPool, i.e.
@@ -434,38 +460,17 @@ class Perceived(Wrapper):
         infos = dict(infos, terminal_observation=p_term)
         return {"obs": p_obs}, reward, dones, infos
 
-    def state_dict(self) -> dict:
-        """The inner wrapper's state and the channels' (ring, age, outputs, call), on the CPU."""
-        out = {"inner": self.env.state_dict(), "channel": self.channel.state_dict()}
-        if self.opponent_channel is not None:
-            out["opponent_channel"] = self.opponent_channel.state_dict()
-        return out
-
-    def load_state_dict(self, state: dict) -> None:
-        from vss_amd.checkpoint import entry
-        self.env.load_state_dict(entry(state, "inner", "Perceived"))
-        self.channel.load_state_dict(entry(state, "channel", "Perceived"))
-        if self.opponent_channel is not None:
-            self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Perceived"))
 
 
-class _EstimatedTeam:
-    """A policy team behind the yellow estimation channel: it acts on the estimated opponent rows, whatever rows it
-    is handed; everything else (check_env, observe, state, version ...) is the team's own."""
-
-    def __init__(self, team, channel):
-        self.team, self.channel = team, channel
+class _EstimatedTeam(_ChannelTeam):
+    """Behind the yellow estimation channel: the team acts on the estimated opponent rows, whatever rows it is
+    handed."""
 
     def __call__(self, act, obs):
         self.team(act, self.channel.obs_out.view(obs.shape))
 
-    def __getattr__(self, name):
-        if name in ("team", "channel"):  # not set yet (a copy under construction): no forwarding loop
-            raise AttributeError(name)
-        return getattr(self.team, name)
 
-
-class Estimated(Wrapper):
+class Estimated(_ChannelWrapper):
     """Dead reckoning round `Perceived` (vss_amd/estimate.py): `obs` and info["terminal_observation"]
     become the perceived rows rolled forward to the present -- by the rows' age, with the project's own drive model
     and the commands given in the meantime -- by one vss_estimate launch per step.  Rewards, dones and every other
@@ -488,14 +493,6 @@ class Estimated(Wrapper):
                                            done_stride=env.channel.done_stride)
         self.opponent_channel = None
         self.channel.start(env.channel.obs_out.view(self._base._obs.shape))  # as Perceived's constructor starts its own
-
-    @property
-    def _opp_obs(self):
-        return self.env._opp_obs
-
-    @property
-    def _opp_act(self):
-        return self.env._opp_act
 
     def _perceived_opponent_rows(self):
         return self.env.opponent_channel.obs_out.view(self.env._opp_obs.shape)
@@ -534,24 +531,12 @@ class Estimated(Wrapper):
         infos = dict(infos, terminal_observation=e_term)
         return {"obs": e_obs}, reward, dones, infos
 
-    def state_dict(self) -> dict:
-        """The inner wrappers' state and the channels' (ring, age, outputs, call), on the CPU."""
-        out = {"inner": self.env.state_dict(), "channel": self.channel.state_dict()}
-        if self.opponent_channel is not None:
-            out["opponent_channel"] = self.opponent_channel.state_dict()
-        return out
-
-    def load_state_dict(self, state: dict) -> None:
-        from vss_amd.checkpoint import entry
-        self.env.load_state_dict(entry(state, "inner", "Estimated"))
-        self.channel.load_state_dict(entry(state, "channel", "Estimated"))
-        if self.opponent_channel is not None:
-            self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Estimated"))
 
 
-class _ActuatedTeam:
-    """A policy team in front of the yellow channel: what it commands passes the channel in place before the step
-    reads it; everything else (check_env, observe, state, version ...) is the team's own."""
+class _ActuatedTeam(_ChannelTeam):
+    """In front of the yellow actuation channel: what the team commands passes the channel in place before the step
+    reads it."""
+    _own = ("team", "channel", "dones")
 
     def __init__(self, team, channel, dones):
         self.team, self.channel, self.dones = team, channel, dones
@@ -560,13 +545,8 @@ class _ActuatedTeam:
         self.team(act, obs)
         self.channel.actuate(act, self.dones, out=act)
 
-    def __getattr__(self, name):
-        if name in ("team", "channel", "dones"):  # not set yet (a copy under construction): no forwarding loop
-            raise AttributeError(name)
-        return getattr(self.team, name)
 
-
-class Actuated(Wrapper):
+class Actuated(_ChannelWrapper):
     """Motor gain, command noise, quantisation, deadband and packet loss between the policy and the step
     (vss_amd/actuate.py): step(action) takes the learner's commands through one vss_actuate launch
     and steps the inner env with what the wheels apply.  `action` itself is not modified (the rollout keeps it for
@@ -596,14 +576,6 @@ class Actuated(Wrapper):
         self.params, self.seed = A.Params(*params), int(seed)
         self.channel = A.ActuationChannel(n, layout, self.params, self.seed, vss.device, done_stride=stride)
         self.opponent_channel = None
-
-    @property
-    def _opp_obs(self):
-        return self.env._opp_obs
-
-    @property
-    def _opp_act(self):
-        return self.env._opp_act
 
     def set_opponent(self, team=None, actuated=None):
         """The inner wrapper's set_opponent; `actuated` (default: a SnapshotOpponent or an OpponentPool, i.e. a
@@ -635,19 +607,6 @@ class Actuated(Wrapper):
     def step(self, action):
         return self.env.step(self.channel.actuate(action, self._dones_prev))
 
-    def state_dict(self) -> dict:
-        """The inner wrapper's state and the channels' (held, gain, episode, output, call, start flag), on the CPU."""
-        out = {"inner": self.env.state_dict(), "channel": self.channel.state_dict()}
-        if self.opponent_channel is not None:
-            out["opponent_channel"] = self.opponent_channel.state_dict()
-        return out
-
-    def load_state_dict(self, state: dict) -> None:
-        from vss_amd.checkpoint import entry
-        self.env.load_state_dict(entry(state, "inner", "Actuated"))
-        self.channel.load_state_dict(entry(state, "channel", "Actuated"))
-        if self.opponent_channel is not None:
-            self.opponent_channel.load_state_dict(entry(state, "opponent_channel", "Actuated"))
 
 
 class _MirrorWrapper(Wrapper):

@@ -53,14 +53,68 @@ CSRC = os.path.join(os.path.dirname(HERE), "csrc")
 HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "vss.h")
 
 
-def _stamped() -> tuple:
-    """The files the Makefile stamps into the library, in its order: the words of its STAMPED line, each without
+REBUILD = "`make -C {csrc}` or `python -c 'import __graft_entry__ as g; g.build()'`"
+
+
+# ---- the stamp and the loader, once: this module, actuate.py and estimate.py wrap them with their own globals ----
+def read_stamped(csrc: str) -> tuple:
+    """The files `csrc`/Makefile stamps into its library, in its order: the words of its STAMPED line, each without
     the ":<flag set>" a translation unit carries there."""
-    with open(os.path.join(CSRC, "Makefile")) as f:
+    with open(os.path.join(csrc, "Makefile")) as f:
         line = re.search(r"^STAMPED\s*:?=\s*(\S.*)$", f.read(), re.M)
     if not line:
-        raise NativeError(f"{CSRC}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
-    return tuple(os.path.normpath(os.path.join(CSRC, word.split(":")[0])) for word in line.group(1).split())
+        raise NativeError(f"{csrc}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
+    return tuple(os.path.normpath(os.path.join(csrc, word.split(":")[0])) for word in line.group(1).split())
+
+
+def hash_files(paths) -> str:
+    """sha256 (first 16 hex digits) of the files' bytes, in order."""
+    h = hashlib.sha256()
+    for path in paths:
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
+
+
+def check_stamp(lib, symbol: str, want: str, lib_path: str) -> None:
+    """Raise unless `lib`'s `symbol`() returns `want` (a stale prebuilt .so, or one older than the stamp)."""
+    try:
+        fn = getattr(lib, symbol)
+    except AttributeError:  # a library older than the stamp: stale by definition
+        built = f"<no {symbol} symbol>"
+    else:
+        fn.restype = ctypes.c_char_p
+        built = fn().decode()
+    if built != want:
+        raise NativeError(f"{lib_path} was built from other sources (stamp {built}, tree {want}); rebuild it with "
+                          + REBUILD.format(csrc=CSRC))
+
+
+def bind_abi(lib: ctypes.CDLL, abi, header: str) -> ctypes.CDLL:
+    try:
+        return cheader.bind(lib, abi)
+    except AttributeError as e:
+        raise NativeError(f"{getattr(lib, '_name', lib)} lacks an entry point that {header} declares: {e}") from None
+
+
+def load_stamped(name: str, noun: str, lib_path: str, verify, abi, header: str, version_fn: str, version: int) -> ctypes.CDLL:
+    """Load the library `name` (the VSS `noun` library) from `lib_path`: raises if it has not been built, if
+    `verify(lib)` refuses its source stamp, if it lacks an entry point of `header`, or if its `version_fn`() is not
+    `version`."""
+    if not os.path.exists(lib_path):
+        raise NativeError(f"VSS {noun} library not found at {lib_path}; build it with " + REBUILD.format(csrc=CSRC))
+    L = ctypes.CDLL(lib_path)
+    verify(L)
+    bind_abi(L, abi, header)
+    built = getattr(L, version_fn)()
+    if built != version:
+        raise NativeError(f"{name} ABI {built} != expected {version}")
+    return L
+
+
+def _stamped() -> tuple:
+    """The files csrc/Makefile stamps into libvss_amd.so, in its order."""
+    return read_stamped(CSRC)
 
 
 STAMPED = _stamped()
@@ -77,53 +131,25 @@ _lib = None
 
 def source_hash() -> str:
     """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
-    h = hashlib.sha256()
-    for path in STAMPED:
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
+    return hash_files(STAMPED)
 
 
 def verify_source_hash(lib: ctypes.CDLL, expected: str | None = None) -> None:
     """Raise unless the library was built from the tree's sources (a stale prebuilt .so)."""
-    want = source_hash() if expected is None else expected
-    try:
-        fn = lib.vss_source_hash
-    except AttributeError:  # a library older than the stamp: stale by definition
-        fn = None
-    if fn is not None:
-        fn.restype = ctypes.c_char_p
-    built = fn().decode() if fn is not None else "<no vss_source_hash symbol>"
-    if built != want:
-        raise NativeError(
-            f"{LIB_PATH} was built from other sources (stamp {built}, tree {want}); rebuild it with "
-            f"`make -C {CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`")
+    check_stamp(lib, "vss_source_hash", source_hash() if expected is None else expected, LIB_PATH)
 
 
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Set the header's restype / argtypes on `lib` (this library, or a variant build of the same ABI)."""
-    try:
-        return cheader.bind(lib, ABI)
-    except AttributeError as e:
-        raise NativeError(f"{getattr(lib, '_name', lib)} lacks an entry point that {HEADER} declares: {e}") from None
+    return bind_abi(lib, ABI, HEADER)
 
 
 def load() -> ctypes.CDLL:
     """Load libvss_amd.so (raises if it has not been built, or was built from other sources)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NativeError(
-            f"VSS HIP library not found at {LIB_PATH}; build it with "
-            f"`make -C {CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = ctypes.CDLL(LIB_PATH)
-    verify_source_hash(L)
-    bind(L)
-    if L.vss_abi_version() != ABI_VERSION:
-        raise NativeError(f"libvss_amd ABI {L.vss_abi_version()} != expected {ABI_VERSION}")
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = load_stamped("libvss_amd", "HIP", LIB_PATH, verify_source_hash, ABI, HEADER, "vss_abi_version", ABI_VERSION)
+    return _lib
 
 
 def check(rc: int, what: str) -> None:

@@ -6,7 +6,8 @@ and two motors of one robot differ by several percent.  The channel turns the co
 the commands the wheels apply, in one launch per call, between the policy and the step.  `reference_actuate` below is
 its specification: float32 numpy, one operation per line, in the kernel's order; the kernel equals it bit for bit
 (tests/test_actuate_gpu.py).  Only + - * /, rint, comparisons, selects, integer operations and perceive.py's Philox /
-Box-Muller restatement occur, every one correctly rounded in both, and nothing is contracted into an FMA.
+Box-Muller (the kernel's: csrc/vss_numerics.h) occur, every one correctly rounded in both, and nothing is contracted
+into an FMA.
 
     ch = ActuationChannel(n_fields, Layout(...), Params(...), seed, device)
     ch.start()                                   # reset(): the next call begins an episode in every field
@@ -27,16 +28,14 @@ libvss_amd.so stay exactly as they are.
 from __future__ import annotations
 
 import ctypes
-import hashlib
 import os
-import re
 from typing import NamedTuple
 
 import numpy as np
 import torch  # noqa: F401  (loads torch's HIP runtime before the library resolves it, as vss_amd/_native.py)
 
 from . import _native as N
-from . import cheader
+from . import channel, cheader
 from .perceive import _box_muller, _philox, _u01
 
 F = np.float32
@@ -55,11 +54,7 @@ HEADER = os.path.join(os.path.dirname(N.HEADER), "vss_actuate.h")
 
 def _stamped() -> tuple:
     """The files csrc/actuate/Makefile stamps into the library, in its order (as _native._stamped for the core)."""
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        line = re.search(r"^STAMPED\s*:?=\s*(\S.*)$", f.read(), re.M)
-    if not line:
-        raise N.NativeError(f"{CSRC}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
-    return tuple(os.path.normpath(os.path.join(CSRC, word.split(":")[0])) for word in line.group(1).split())
+    return N.read_stamped(CSRC)
 
 
 STAMPED = _stamped()
@@ -77,48 +72,21 @@ _lib = None
 
 def source_hash() -> str:
     """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
-    h = hashlib.sha256()
-    for path in STAMPED:
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
+    return N.hash_files(STAMPED)
 
 
 def verify_source_hash(lib, expected: str | None = None) -> None:
     """Raise unless the library was built from the tree's sources (a stale prebuilt .so)."""
-    want = source_hash() if expected is None else expected
-    try:
-        fn = lib.vss_actuate_source_hash
-    except AttributeError:
-        fn = None
-    if fn is not None:
-        fn.restype = ctypes.c_char_p
-    built = fn().decode() if fn is not None else "<no vss_actuate_source_hash symbol>"
-    if built != want:
-        raise N.NativeError(
-            f"{LIB_PATH} was built from other sources (stamp {built}, tree {want}); rebuild it with "
-            f"`make -C {N.CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`")
+    N.check_stamp(lib, "vss_actuate_source_hash", source_hash() if expected is None else expected, LIB_PATH)
 
 
 def load() -> ctypes.CDLL:
     """Load libvss_actuate.so (raises if it has not been built, or was built from other sources)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise N.NativeError(
-            f"VSS actuation library not found at {LIB_PATH}; build it with "
-            f"`make -C {N.CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = ctypes.CDLL(LIB_PATH)
-    verify_source_hash(L)
-    try:
-        cheader.bind(L, ABI)
-    except AttributeError as e:
-        raise N.NativeError(f"{LIB_PATH} lacks an entry point that {HEADER} declares: {e}") from None
-    if L.vss_actuate_abi_version() != ABI_VERSION:
-        raise N.NativeError(f"libvss_actuate ABI {L.vss_actuate_abi_version()} != expected {ABI_VERSION}")
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = N.load_stamped("libvss_actuate", "actuation", LIB_PATH, verify_source_hash, ABI, HEADER,
+                              "vss_actuate_abi_version", ABI_VERSION)
+    return _lib
 
 
 class Layout(NamedTuple):
@@ -131,14 +99,11 @@ class Layout(NamedTuple):
 
     def span(self, n_fields: int) -> int:
         """Robots from the first command to the last one's end."""
-        return (self.n_teams - 1) * self.team_stride + max(n_fields - 1, 0) * self.field_stride + self.robots
+        return channel.span(self, n_fields)
 
     def index(self, n_fields: int) -> np.ndarray:
         """(n_teams, n_fields, robots) int64: the robot slot of team block b, field f, robot k."""
-        b = np.arange(self.n_teams, dtype=np.int64)[:, None, None]
-        f = np.arange(n_fields, dtype=np.int64)[None, :, None]
-        k = np.arange(self.robots, dtype=np.int64)[None, None, :]
-        return b * self.team_stride + f * self.field_stride + k
+        return channel.index(self, n_fields)
 
 
 class Params(NamedTuple):
@@ -299,12 +264,14 @@ def reference_actuate(cmd, done_prev, held, gain, episode, call: int, params, se
 
 
 # ---- the kernel's side ----------------------------------------------------------------------------------------------
-class ActuationChannel:
+class ActuationChannel(channel.Channel):
     """held, gain, episode, the output buffer and the host call counter of one set of commands.
 
     `rows`: the robots (2 floats each) of the buffers handed to actuate() (default: the layout's span); the output has
     that many and is returned in the input's shape; what the layout does not cover stays zero there.  `done_stride`:
     int64 elements from one field's done flag to the next."""
+    unit, width = "robots", 2
+    scalars = {"call": int, "fresh": bool}  # the call counter and the start flag
 
     def __init__(self, n_fields: int, layout, params=Params(), seed: int = 0, device="cuda", done_stride: int = 1,
                  rows: int | None = None):
@@ -313,11 +280,8 @@ class ActuationChannel:
         self.n_fields, self.layout, self.params = int(n_fields), Layout(*layout), Params(*params).check()
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.done_stride = int(done_stride)
-        lay = self.layout
-        self.rows = lay.span(self.n_fields) if rows is None else int(rows)
-        if self.rows < lay.span(self.n_fields):
-            raise ValueError(f"the layout spans {lay.span(self.n_fields)} robots, the buffers have {self.rows}")
-        dev = self.device
+        self._set_rows(rows)
+        lay, dev = self.layout, self.device
         packed = (lay.n_teams, self.n_fields, lay.robots, 2)
         self.held = torch.zeros(packed, device=dev)
         self.gain = torch.ones(packed, device=dev)
@@ -355,9 +319,7 @@ class ActuationChannel:
         dst = self.out if out is None else cmd
         done_ptr = None
         if not self.fresh:
-            need = (self.n_fields - 1) * self.done_stride + 1 if self.n_fields else 0
-            if (done_prev is None or done_prev.dtype != torch.long or done_prev.device != self.out.device
-                    or not done_prev.is_contiguous() or done_prev.numel() < need):
+            if not self._done_ok(done_prev):
                 raise ValueError(f"done_prev must be contiguous int64 with a flag every {self.done_stride} elements for "
                                  f"{self.n_fields} fields (start() makes the next call a start call)")
             done_ptr = done_prev.data_ptr()
@@ -371,14 +333,3 @@ class ActuationChannel:
 
     def _state_tensors(self) -> dict:
         return dict(held=self.held, gain=self.gain, episode=self.episode, out=self.out)
-
-    def state_dict(self) -> dict:
-        """held, gain, episode and the output on the CPU, the call counter and the start flag."""
-        from .checkpoint import to_cpu
-        return dict(to_cpu(self._state_tensors()), call=int(self.call), fresh=bool(self.fresh))
-
-    def load_state_dict(self, state: dict) -> None:
-        from .checkpoint import copy_entries, entry
-        copy_entries("ActuationChannel", self._state_tensors(), state)
-        self.call = int(entry(state, "call", "ActuationChannel"))
-        self.fresh = bool(entry(state, "fresh", "ActuationChannel"))

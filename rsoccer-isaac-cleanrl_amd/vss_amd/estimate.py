@@ -7,8 +7,8 @@ current step's commands.  This channel turns each such row (state of call t - L)
 call t, by running the project's own drive model L times with the commands of calls
 t - L + 1 .. t, in one launch per call.  `reference_estimate` below is its specification: float32 numpy, one
 operation per line, in the kernel's order; the kernel equals it bit for bit (tests/test_estimate_gpu.py).  Only
-+ - * /, comparisons, selects, integer operations and perceive.py's `_sincos_small` occur, every one correctly
-rounded in both, and nothing is contracted into an FMA.
++ - * /, comparisons, selects, integer operations and perceive.py's `_sincos_small` (the kernel's: csrc/vss_numerics.h)
+occur, every one correctly rounded in both, and nothing is contracted into an FMA.
 
     ch = EstimationChannel(n_fields, Layout(...), delay, device)
     rows = ch.start(obs)                            # reset(): ages 0, the ring's slot, obs itself
@@ -31,16 +31,14 @@ include/vss.h, libvss_amd.so and libvss_actuate.so stay exactly as they are.
 from __future__ import annotations
 
 import ctypes
-import hashlib
 import os
-import re
 from typing import NamedTuple
 
 import numpy as np
 import torch  # noqa: F401  (loads torch's HIP runtime before the library resolves it, as vss_amd/_native.py)
 
 from . import _native as N
-from . import cheader
+from . import channel, cheader
 from . import perceive as _P
 from .perceive import ACTION_FLOATS, NUM_OBS, _sincos_small
 
@@ -57,11 +55,7 @@ HEADER = os.path.join(os.path.dirname(N.HEADER), "vss_estimate.h")
 
 def _stamped() -> tuple:
     """The files csrc/estimate/Makefile stamps into the library, in its order (as _native._stamped for the core)."""
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        line = re.search(r"^STAMPED\s*:?=\s*(\S.*)$", f.read(), re.M)
-    if not line:
-        raise N.NativeError(f"{CSRC}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
-    return tuple(os.path.normpath(os.path.join(CSRC, word.split(":")[0])) for word in line.group(1).split())
+    return N.read_stamped(CSRC)
 
 
 STAMPED = _stamped()
@@ -78,48 +72,21 @@ _lib = None
 
 def source_hash() -> str:
     """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
-    h = hashlib.sha256()
-    for path in STAMPED:
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
+    return N.hash_files(STAMPED)
 
 
 def verify_source_hash(lib, expected: str | None = None) -> None:
     """Raise unless the library was built from the tree's sources (a stale prebuilt .so)."""
-    want = source_hash() if expected is None else expected
-    try:
-        fn = lib.vss_estimate_source_hash
-    except AttributeError:
-        fn = None
-    if fn is not None:
-        fn.restype = ctypes.c_char_p
-    built = fn().decode() if fn is not None else "<no vss_estimate_source_hash symbol>"
-    if built != want:
-        raise N.NativeError(
-            f"{LIB_PATH} was built from other sources (stamp {built}, tree {want}); rebuild it with "
-            f"`make -C {N.CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`")
+    N.check_stamp(lib, "vss_estimate_source_hash", source_hash() if expected is None else expected, LIB_PATH)
 
 
 def load() -> ctypes.CDLL:
     """Load libvss_estimate.so (raises if it has not been built, or was built from other sources)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise N.NativeError(
-            f"VSS estimation library not found at {LIB_PATH}; build it with "
-            f"`make -C {N.CSRC}` or `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = ctypes.CDLL(LIB_PATH)
-    verify_source_hash(L)
-    try:
-        cheader.bind(L, ABI)
-    except AttributeError as e:
-        raise N.NativeError(f"{LIB_PATH} lacks an entry point that {HEADER} declares: {e}") from None
-    if L.vss_estimate_abi_version() != ABI_VERSION:
-        raise N.NativeError(f"libvss_estimate ABI {L.vss_estimate_abi_version()} != expected {ABI_VERSION}")
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = N.load_stamped("libvss_estimate", "estimation", LIB_PATH, verify_source_hash, ABI, HEADER,
+                              "vss_estimate_abi_version", ABI_VERSION)
+    return _lib
 
 
 class Layout(NamedTuple):
@@ -132,11 +99,11 @@ class Layout(NamedTuple):
 
     def span(self, n_fields: int) -> int:
         """Rows from the first row to the last one's end."""
-        return (self.n_teams - 1) * self.team_stride + max(n_fields - 1, 0) * self.field_stride + self.robots
+        return channel.span(self, n_fields)
 
     def row_index(self, n_fields: int) -> np.ndarray:
         """(n_teams, n_fields, robots) int64: the row of team block b, field f, robot k."""
-        return _P.Layout(*self).row_index(n_fields)
+        return channel.index(self, n_fields)
 
 
 def of_perception(layout) -> Layout:
@@ -292,7 +259,7 @@ def reference_estimate(obs, term, done, hist, age, call: int, delay: int):
 
 
 # ---- the kernel's side ----------------------------------------------------------------------------------------------
-class EstimationChannel:
+class EstimationChannel(channel.Channel):
     """The command ring, the ages, the outputs and the host call counter of one set of rows.
 
     `rows`: the rows of the buffers handed to start() / estimate() (default: the layout's span); the outputs have that
@@ -306,11 +273,8 @@ class EstimationChannel:
         self.done_stride = int(done_stride)
         if not 0 <= self.delay <= MAX_DELAY:
             raise ValueError(f"estimation: the delay must be in 0..{MAX_DELAY} steps, got {delay}")
-        lay = self.layout
-        self.rows = lay.span(self.n_fields) if rows is None else int(rows)
-        if self.rows < lay.span(self.n_fields):
-            raise ValueError(f"the layout spans {lay.span(self.n_fields)} rows, the buffers have {self.rows}")
-        dev = self.device
+        self._set_rows(rows)
+        lay, dev = self.layout, self.device
         packed = (lay.n_teams, self.n_fields, lay.robots)
         self.hist = torch.zeros((self.delay,) + packed + (6,), device=dev)
         self.age = torch.zeros(packed, dtype=torch.int32, device=dev)
@@ -319,12 +283,6 @@ class EstimationChannel:
         self.call = 0
         self._no_done = torch.zeros(1, dtype=torch.long, device=dev)
         self._lay = VssEstimateLayout(int(lay.field_stride), int(lay.team_stride), int(lay.robots), int(lay.n_teams))
-
-    def _check_rows(self, t: torch.Tensor, name: str) -> None:
-        if (t.dtype != torch.float32 or t.device != self.obs_out.device or not t.is_contiguous()
-                or t.numel() != self.rows * NUM_OBS):
-            raise ValueError(f"{name} must be {self.rows} contiguous float32 rows of {NUM_OBS} on {self.obs_out.device}, "
-                             f"got {tuple(t.shape)} {t.dtype} on {t.device}")
 
     def _launch(self, obs, term, done) -> None:
         rc = load().vss_estimate(
@@ -348,22 +306,9 @@ class EstimationChannel:
         """One step: (estimated obs, estimated terminal obs) in the inputs' shapes; the buffers are the channel's."""
         self._check_rows(obs, "obs")
         self._check_rows(term, "term")
-        need = (self.n_fields - 1) * self.done_stride + 1 if self.n_fields else 0
-        if done.dtype != torch.long or done.device != self.obs_out.device or not done.is_contiguous() or done.numel() < need:
-            raise ValueError(f"done must be contiguous int64 with a flag every {self.done_stride} elements for "
-                             f"{self.n_fields} fields, got {tuple(done.shape)} {done.dtype}")
+        self._check_done(done)
         self._launch(obs, term, done)
         return self.obs_out.view(obs.shape), self.term_out.view(term.shape)
 
     def _state_tensors(self) -> dict:
         return dict(hist=self.hist, age=self.age, obs_out=self.obs_out, term_out=self.term_out)
-
-    def state_dict(self) -> dict:
-        """The ring, the ages, the outputs (the next rollout's first input) and the call counter, on the CPU."""
-        from .checkpoint import to_cpu
-        return dict(to_cpu(self._state_tensors()), call=int(self.call))
-
-    def load_state_dict(self, state: dict) -> None:
-        from .checkpoint import copy_entries, entry
-        copy_entries("EstimationChannel", self._state_tensors(), state)
-        self.call = int(entry(state, "call", "EstimationChannel"))

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import channel
 
 F = np.float32
 U32 = np.uint32
@@ -52,14 +53,11 @@ class Layout(NamedTuple):
 
     def span(self, n_fields: int) -> int:
         """Rows from the first row to the last one's end."""
-        return (self.n_teams - 1) * self.team_stride + max(n_fields - 1, 0) * self.field_stride + self.robots
+        return channel.span(self, n_fields)
 
     def row_index(self, n_fields: int) -> np.ndarray:
         """(n_teams, n_fields, robots) int64: the row of team block b, field f, robot k."""
-        b = np.arange(self.n_teams, dtype=np.int64)[:, None, None]
-        f = np.arange(n_fields, dtype=np.int64)[None, :, None]
-        k = np.arange(self.robots, dtype=np.int64)[None, None, :]
-        return b * self.team_stride + f * self.field_stride + k
+        return channel.index(self, n_fields)
 
 
 class Noise(NamedTuple):
@@ -114,7 +112,7 @@ def full_rows(ball, robots) -> np.ndarray:
     return out
 
 
-# ---- the draws: vss_step.hip's Philox and Box-Muller, restated ---------------------------------------------------
+# ---- the draws: csrc/vss_numerics.h's Philox, sin / cos / log and unit Box-Muller, one operation per line -------
 def _philox(k0, k1, c0, c1, c2, c3):
     """Philox4x32-10 on uint32 arrays (key and counter words broadcast together)."""
     c0, c1, c2, c3, k0, k1 = (np.asarray(v, dtype=U32) for v in np.broadcast_arrays(c0, c1, c2, c3, k0, k1))
@@ -312,7 +310,7 @@ def _c_layout(layout: Layout) -> N.VssPerceiveLayout:
                                int(layout.first_team))
 
 
-class PerceptionChannel:
+class PerceptionChannel(channel.Channel):
     """The ring, the ages, the outputs and the host call counter of one set of rows.
 
     `rows`: the rows of the buffers handed to start() / perceive() (default: the layout's span); the outputs have
@@ -329,11 +327,8 @@ class PerceptionChannel:
             raise ValueError(f"observation delay must be in 0..{MAX_DELAY} steps, got {delay}")
         if any(not (float(s) >= 0.0 and float(s) < float("inf")) for s in self.noise):
             raise ValueError(f"observation noise: the standard deviations must be finite and >= 0, got {tuple(self.noise)}")
-        lay = self.layout
-        self.rows = lay.span(self.n_fields) if rows is None else int(rows)
-        if self.rows < lay.span(self.n_fields):
-            raise ValueError(f"the layout spans {lay.span(self.n_fields)} rows, the buffers have {self.rows}")
-        dev = self.device
+        self._set_rows(rows)
+        lay, dev = self.layout, self.device
         self.ring = torch.zeros((self.delay + 1, lay.n_teams, self.n_fields, lay.robots, NUM_OBS), device=dev)
         self.age = torch.zeros(self.n_fields, dtype=torch.int32, device=dev)
         self.obs_out = torch.zeros((self.rows, NUM_OBS), device=dev)
@@ -341,12 +336,6 @@ class PerceptionChannel:
         self.call = 0
         self._no_done = torch.zeros(1, dtype=torch.long, device=dev)
         self._lay, self._noise = _c_layout(lay), N.VssPerceiveNoise(*(float(s) for s in self.noise))
-
-    def _check_rows(self, t: torch.Tensor, name: str) -> None:
-        if (t.dtype != torch.float32 or t.device != self.obs_out.device or not t.is_contiguous()
-                or t.numel() != self.rows * NUM_OBS):
-            raise ValueError(f"{name} must be {self.rows} contiguous float32 rows of {NUM_OBS} on {self.obs_out.device}, "
-                             f"got {tuple(t.shape)} {t.dtype} on {t.device}")
 
     def _launch(self, obs, term, done) -> None:
         rc = N.load().vss_perceive(
@@ -370,22 +359,9 @@ class PerceptionChannel:
         """One step: (perceived obs, perceived terminal obs) in the inputs' shapes; the buffers are the channel's."""
         self._check_rows(obs, "obs")
         self._check_rows(term, "term")
-        need = (self.n_fields - 1) * self.done_stride + 1 if self.n_fields else 0
-        if done.dtype != torch.long or done.device != self.obs_out.device or not done.is_contiguous() or done.numel() < need:
-            raise ValueError(f"done must be contiguous int64 with a flag every {self.done_stride} elements for "
-                             f"{self.n_fields} fields, got {tuple(done.shape)} {done.dtype}")
+        self._check_done(done)
         self._launch(obs, term, done)
         return self.obs_out.view(obs.shape), self.term_out.view(term.shape)
 
     def _state_tensors(self) -> dict:
         return dict(ring=self.ring, age=self.age, obs_out=self.obs_out, term_out=self.term_out)
-
-    def state_dict(self) -> dict:
-        """Ring, age, the outputs (the next rollout's first input) and the call counter, on the CPU."""
-        from .checkpoint import to_cpu
-        return dict(to_cpu(self._state_tensors()), call=int(self.call))
-
-    def load_state_dict(self, state: dict) -> None:
-        from .checkpoint import copy_entries, entry
-        copy_entries("PerceptionChannel", self._state_tensors(), state)
-        self.call = int(entry(state, "call", "PerceptionChannel"))

@@ -44,14 +44,15 @@ def test_header_declares_the_expected_entry_points():
 
 def test_stamped_is_the_makefiles_list():
     """N.STAMPED is csrc/Makefile's STAMPED line, in its order: the nine kernel sources, the shared row header, the
-    ABI header and the Makefile itself."""
+    shared numerics header, the ABI header, the Makefile itself and the rules it includes."""
     with open(os.path.join(N.CSRC, "Makefile")) as f:
         (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
     files = [w.split(":")[0] for w in line.split()]
     assert list(N.STAMPED) == [os.path.normpath(os.path.join(N.CSRC, w)) for w in files]
     assert [os.path.basename(p) for p in N.STAMPED] == [
         "vss_step.hip", "vss_update.hip", "vss_policy.hip", "vss_gemm_x6.hip", "vss_loss.hip", "vss_optim.hip",
-        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_loss_row.h", "vss.h", "Makefile"]
+        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_loss_row.h", "vss_numerics.h", "vss.h", "Makefile",
+        "stamped.mk"]
     assert N.HEADER in N.STAMPED and all(os.path.isfile(p) for p in N.STAMPED)
     hips = sorted(f for f in os.listdir(N.CSRC) if f.endswith(".hip"))
     assert hips == sorted(f for f in files if f.endswith(".hip"))  # no kernel source left out of the stamp

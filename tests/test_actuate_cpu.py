@@ -99,8 +99,10 @@ def test_the_core_header_and_library_are_as_they_were():
 def test_the_stamp_covers_the_makefiles_list_and_a_stale_library_is_refused_at_load(tmp_path, monkeypatch):
     with open(os.path.join(A.CSRC, "Makefile")) as f:
         (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
-    assert line.split() == ["vss_actuate.hip:STEP_FLAGS", "../../../include/vss_actuate.h", "../../../include/vss.h", "Makefile"]
-    assert [os.path.basename(p) for p in A.STAMPED] == ["vss_actuate.hip", "vss_actuate.h", "vss.h", "Makefile"]
+    assert line.split() == ["vss_actuate.hip:STEP_FLAGS", "../vss_numerics.h", "../../../include/vss_actuate.h", "../../../include/vss.h",
+                            "Makefile", "../stamped.mk"]
+    assert [os.path.basename(p) for p in A.STAMPED] == ["vss_actuate.hip", "vss_numerics.h", "vss_actuate.h", "vss.h", "Makefile",
+                                                        "stamped.mk"]
     assert A.HEADER in A.STAMPED and N.HEADER in A.STAMPED and all(os.path.isfile(p) for p in A.STAMPED)
     lib = A.load()
     A.verify_source_hash(lib)

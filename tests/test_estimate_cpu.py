@@ -85,10 +85,12 @@ def test_the_core_header_and_the_other_libraries_stamps_are_as_they_were():
     assert len(h.functions) == 61 and len(h.structs) == 10
     assert not any("estimate" in name for name in list(h.functions) + list(h.structs) + list(N.EXPORTED))
     assert not any("estimate" in p for p in N.STAMPED + A.STAMPED)
-    assert [os.path.basename(p) for p in A.STAMPED] == ["vss_actuate.hip", "vss_actuate.h", "vss.h", "Makefile"]
+    assert [os.path.basename(p) for p in A.STAMPED] == ["vss_actuate.hip", "vss_numerics.h", "vss_actuate.h", "vss.h", "Makefile",
+                                                        "stamped.mk"]
     assert [os.path.basename(p) for p in N.STAMPED] == [
         "vss_step.hip", "vss_update.hip", "vss_policy.hip", "vss_gemm_x6.hip", "vss_loss.hip", "vss_optim.hip",
-        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_loss_row.h", "vss.h", "Makefile"]
+        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_loss_row.h", "vss_numerics.h", "vss.h", "Makefile",
+        "stamped.mk"]
     if shutil.which("nm"):
         assert exported(N.LIB_PATH, "vss_") == sorted(h.functions)
 
@@ -96,8 +98,10 @@ def test_the_core_header_and_the_other_libraries_stamps_are_as_they_were():
 def test_the_stamp_covers_the_makefiles_list_and_a_stale_library_is_refused_at_load(tmp_path, monkeypatch):
     with open(os.path.join(E.CSRC, "Makefile")) as f:
         (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
-    assert line.split() == ["vss_estimate.hip:STEP_FLAGS", "../../../include/vss_estimate.h", "../../../include/vss.h", "Makefile"]
-    assert [os.path.basename(p) for p in E.STAMPED] == ["vss_estimate.hip", "vss_estimate.h", "vss.h", "Makefile"]
+    assert line.split() == ["vss_estimate.hip:STEP_FLAGS", "../vss_numerics.h", "../../../include/vss_estimate.h", "../../../include/vss.h",
+                            "Makefile", "../stamped.mk"]
+    assert [os.path.basename(p) for p in E.STAMPED] == ["vss_estimate.hip", "vss_numerics.h", "vss_estimate.h", "vss.h", "Makefile",
+                                                        "stamped.mk"]
     assert E.HEADER in E.STAMPED and N.HEADER in E.STAMPED and all(os.path.isfile(p) for p in E.STAMPED)
     lib = E.load()
     E.verify_source_hash(lib)
