@@ -767,6 +767,101 @@ int vss_perceive(void* stream, int64_t n_fields, const vss_perceive_layout* lay,
                  float* ring /* (delay+1, n_teams, n_fields, robots, 52) */, int32_t* age /* (n_fields) */,
                  float* obs_out, float* term_out /* NULL iff term is */);
 
+/* ---------------------------------------------------------------------------------------------
+ * The actuation channel (csrc/vss_actuate.hip; vss_amd/actuate.py): what a VSS robot's wheels
+ * receive of what a policy commands.
+ *
+ * A command is the two floats (left wheel, right wheel) of one robot.  One call takes the commands of one control
+ * step through the channel: the radio's range and 8-bit-like quantisation, the loss of a team's packet (the robot
+ * keeps the command it had), a deadband, the episode's per-wheel motor gains and per-step command noise.
+ * vss_amd/actuate.py reference_actuate is the specification; the kernel equals it bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+#define VSS_ACTUATE_MAX_LEVELS 32767
+
+/* Where the commands lie: strides in robots (2 floats); the command of team block b, field f, robot k is at
+ * base + (b * team_stride + f * field_stride + k) * 2 floats.  team_stride is read with two teams only.
+ *   SA (N,2): 1, -, 1, 1, 0      CMA (N,6), DMA (3N,2): 3, -, 3, 1, 0      opp_act (N,3,2): 3, -, 3, 1, 1
+ *   mirror SA (2N,2): 1, N, 1, 2, 0      mirror CMA (2N,6) / DMA (6N,2): 3, 3N, 3, 2, 0
+ *   the blue half of FULL's (N,2,3,2): 6, -, 3, 1, 0 */
+typedef struct vss_actuate_layout {
+  int64_t field_stride;
+  int64_t team_stride;
+  int32_t robots;      /* 1 or 3 */
+  int32_t n_teams;     /* 1 or 2 */
+  int32_t first_team;  /* 0 blue, 1 yellow; block 1 is the other */
+} vss_actuate_layout;
+
+/* gain_sigma in [0, 0.3]: wheel gain 1 + gain_sigma * clamp(z, -3, 3), drawn once per episode (so >= 0.1);
+ * noise_sigma >= 0: added to the applied command every step; deadband in [0, 1]: |command| below it is 0;
+ * loss_prob in [0, 1): a team's packet is lost with this probability; levels in 0..VSS_ACTUATE_MAX_LEVELS:
+ * the command is rounded to a multiple of 1 / levels (0: not quantised).  A zero switches its effect off. */
+typedef struct vss_actuate_params {
+  float gain_sigma, noise_sigma, deadband, loss_prob;
+  int32_t levels;
+} vss_actuate_params;
+
+/* One control step of the channel, one launch.  cmd, out: commands in the layout (out may be cmd itself: in
+ * place; otherwise they must not overlap).  held, gain: (n_teams, n_fields, robots, 2) fp32 packed, the last
+ * received command and the episode's gains; episode: (n_fields) uint32.  done_prev: the int64 done flags the
+ * previous step returned, one every done_stride elements; NULL is the start call (every field begins an episode).
+ * seed, call: the Philox key and the call index of the draws; fields, entities and teams index them, never the
+ * layout, so two channels with one seed and call index act in one world.
+ *
+ * VSS_E_ARG, before any HIP call: a null lay, prm, cmd, held, gain, episode or out; cmd, out, held, gain or
+ * done_prev not 8-B or episode not 4-B aligned; out partly overlapping cmd; held, gain or episode overlapping each
+ * other, cmd, out or done_prev; a parameter outside its range above or not finite; robots not 1 or 3; n_teams not
+ * 1 or 2; first_team not 0 or 1; field_stride < robots; with two teams a team_stride smaller than a block's span;
+ * done_stride < 1 with done_prev given; n_fields < 0; sizes whose grid or byte offsets overflow.
+ * n_fields == 0: VSS_OK, no launch. */
+int vss_actuate(void* stream, int64_t n_fields, const vss_actuate_layout* lay, const vss_actuate_params* prm,
+                uint64_t seed, uint32_t call, const float* cmd, const int64_t* done_prev, int64_t done_stride,
+                float* held, float* gain, uint32_t* episode, float* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The estimation channel (csrc/vss_estimate.hip; vss_amd/estimate.py): delayed observation rows
+ * rolled forward to the present with the project's own drive model.
+ *
+ * A row is the 52-float observation row of envs/vss.py compute_obs: ball x y vx vy [0:4]; own robot j at 4 + 9 j:
+ * x y vx vy cos sin w aL aR; opponent j at 31 + 7 j: x y vx vy cos sin w.  A perceived row (vss_perceive) is the state
+ * of `lead` control steps ago, but its six own-action floats (11, 12, 20, 21, 29, 30) are the current step's
+ * commands.  One call turns each row into an estimate of the present: DESIGN.md §3's drive, damping and integration
+ * steps, run `lead` times with the commands the row's team gave in the meantime (kept here, in `hist`), every row in
+ * its own frame and independently of every other.  There are no contacts and no walls.
+ * vss_amd/estimate.py reference_estimate is the specification; the kernel equals it bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+#define VSS_ESTIMATE_MAX_DELAY 15
+
+/* Where the rows lie, as vss_perceive_layout without first_team: strides in 52-float rows; the row of team block b,
+ * field f, robot k is at base + (b * team_stride + f * field_stride + k) * 52 floats, in obs, term and both
+ * outputs.  team_stride is read with two teams only.
+ *   SA, CMA: 1, -, 1, 1      DMA, opp_obs (N,3,52): 3, -, 3, 1      mirror: R, R N, R, 2
+ *   the blue rows of FULL's (N,2,3,52): 6, -, 3, 1 */
+typedef struct vss_estimate_layout {
+  int64_t field_stride;
+  int64_t team_stride;
+  int32_t robots;   /* 1 or 3 */
+  int32_t n_teams;  /* 1 or 2 */
+} vss_estimate_layout;
+
+/* One call of the channel, one launch.  obs, term: the perceived rows of call index `call` (term NULL: the start call
+ * of reset(): every age 0, obs_out = obs, no term_out).  done: the step's int64 done flags, one per field every
+ * done_stride elements (not read by a start call).  hist: (delay, n_teams, n_fields, robots, 6) fp32, a ring of each
+ * row's own-action floats, call t in slot t % delay (not touched for delay 0); age: (n_teams, n_fields, robots) int32,
+ * per row, perception's recurrence.  Per row:
+ *   d = min(age + 1, delay);  age' = done ? 0 : d
+ *   term_out = term rolled forward d steps, obs_out = obs rolled forward age' steps (0 steps: a copy)
+ *   hist[call % delay] = obs's own-action floats
+ *
+ * VSS_E_ARG, before any HIP call: a null lay, obs, done, age or obs_out; hist null with delay >= 1; exactly one of
+ * term / term_out null; a row pointer not 16-B, done or hist not 8-B or age not 4-B aligned; an output (obs_out,
+ * term_out, hist, age) whose byte range overlaps an input's or another output's; delay outside
+ * 0..VSS_ESTIMATE_MAX_DELAY; robots not 1 or 3; n_teams not 1 or 2; field_stride < robots; with two teams a
+ * team_stride smaller than a block's span; done_stride < 1; n_fields < 0; sizes whose grid or byte offsets overflow.
+ * n_fields == 0: VSS_OK, no launch. */
+int vss_estimate(void* stream, int64_t n_fields, const vss_estimate_layout* lay, int32_t delay, uint32_t call,
+                 const float* obs, const float* term, const int64_t* done, int64_t done_stride, float* hist,
+                 int32_t* age, float* obs_out, float* term_out);
+
 #ifdef __cplusplus
 }
 #endif

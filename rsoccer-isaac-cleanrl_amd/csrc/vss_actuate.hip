@@ -1,11 +1,11 @@
-// vss_actuate.hip — the actuation channel in one launch (gfx950): vss_actuate of include/vss_actuate.h.
+// vss_actuate.hip — the actuation channel in one launch (gfx950): vss_actuate of include/vss.h.
 //
 // What a VSS robot's wheels receive of what a policy commands: the radio's range and quantisation, a lost packet
 // (the robot keeps the command it had), a deadband, the episode's per-wheel motor gains and per-step command
 // noise.  vss_amd/actuate.py reference_actuate is the specification -- float32, one operation per line -- and this
 // file follows it line by line: + - * /, rintf, sqrtf, comparisons, selects and integer operations only, all
 // correctly rounded, denormals kept, no FMA contraction (-ffp-contract=off and the pragma below).  The Philox
-// block, u01 and the unit box_muller are ../vss_numerics.h's, shared with vss_perceive.hip and vss_step.hip.  The
+// block, u01 and the unit box_muller are vss_numerics.h's, shared with vss_perceive.hip and vss_step.hip.  The
 // result equals the reference bit for bit (tests/test_actuate_gpu.py, closed loop included).
 //
 //   one field per lane: the lane loops over its n_teams * robots commands with 8-byte loads and stores.  The
@@ -24,8 +24,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../../include/vss_actuate.h"
-#include "../vss_numerics.h"
+#include "../../include/vss.h"
+#include "vss_numerics.h"
 
 #pragma clang fp contract(off)
 
@@ -182,8 +182,6 @@ __global__ __launch_bounds__(kBlock) void actuate_kernel(const Args a) {
 }  // namespace vact
 
 extern "C" {
-
-int vss_actuate_abi_version(void) { return VSS_ACTUATE_ABI_VERSION; }
 
 int vss_actuate(void* stream, int64_t n_fields, const vss_actuate_layout* lay, const vss_actuate_params* prm, uint64_t seed,
                 uint32_t call, const float* cmd, const int64_t* done_prev, int64_t done_stride, float* held, float* gain,

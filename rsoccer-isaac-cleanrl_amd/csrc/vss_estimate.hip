@@ -1,4 +1,4 @@
-// vss_estimate.hip — the estimation channel in one launch (gfx950): vss_estimate of include/vss_estimate.h.
+// vss_estimate.hip — the estimation channel in one launch (gfx950): vss_estimate of include/vss.h.
 //
 // A perceived observation row is the state of `lead` control steps ago; its six own-action floats are the current
 // step's commands.  The channel rolls every row forward to the present with DESIGN.md §3's drive, damping and
@@ -7,7 +7,7 @@
 // operation per line -- and this file follows it line by line: + - * /, comparisons, selects and integer operations
 // only, all correctly rounded, denormals kept, no FMA contraction (-ffp-contract=off and the pragma below).  The
 // drive lines are those of oracle/vss_oracle.c physics_field with (c, s) taken from the row; sincos_small is
-// ../vss_numerics.h's, shared with vss_perceive.hip and vss_step.hip.  The result equals the reference bit for bit
+// vss_numerics.h's, shared with vss_perceive.hip and vss_step.hip.  The result equals the reference bit for bit
 // (tests/test_estimate_gpu.py, closed loop included).
 //
 //   one row per lane.  age and hist are per row, so a lane reads and writes only its own state: no lane depends on
@@ -31,8 +31,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../../include/vss_estimate.h"
-#include "../vss_numerics.h"
+#include "../../include/vss.h"
+#include "vss_numerics.h"
 
 #pragma clang fp contract(off)
 
@@ -233,8 +233,6 @@ inline void launch(int delay, dim3 grid, hipStream_t s, const Args& a) {
 }  // namespace vest
 
 extern "C" {
-
-int vss_estimate_abi_version(void) { return VSS_ESTIMATE_ABI_VERSION; }
 
 int vss_estimate(void* stream, int64_t n_fields, const vss_estimate_layout* lay, int32_t delay, uint32_t call, const float* obs,
                  const float* term, const int64_t* done, int64_t done_stride, float* hist, int32_t* age, float* obs_out,

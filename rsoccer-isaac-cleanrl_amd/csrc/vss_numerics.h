@@ -3,10 +3,10 @@
 //
 // The project's promise is kernel == float32 numpy specification == C oracle, bit for bit.  The draws (Philox4x32-10,
 // the uniforms, Box-Muller) and the transcendental-free sin / cos / log below are on every side of it: vss_step.hip,
-// vss_perceive.hip, actuate/vss_actuate.hip and estimate/vss_estimate.hip include this file, vss_amd/perceive.py
+// vss_perceive.hip, vss_actuate.hip and vss_estimate.hip include this file, vss_amd/perceive.py
 // (_philox .. _box_muller) states the same operations in numpy, one per line, and oracle/vss_oracle.c keeps a copy of
 // its own on purpose: an oracle that shared text with what it checks would check nothing.  An edit here changes all
-// four units at once, and every library's source stamp (this file is on each Makefile's STAMPED line).
+// four units at once, and the library's source stamp (this file is on the Makefile's STAMPED line).
 //
 // Everything is float32 with FMA contraction off: the pragma below covers this file's functions wherever they are
 // inlined, and each including unit is compiled with -ffp-contract=off as well.  A unit pulls the device functions in

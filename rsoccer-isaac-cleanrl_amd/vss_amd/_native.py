@@ -9,9 +9,9 @@ streams.
 
 Nothing of the ABI is written down here: the header is parsed at import (vss_amd/cheader.py), and
   - every `#define VSS_<NAME> <integer>` is the module constant <NAME> (ABI_VERSION, MODE_SA, CH_RX, STATE_CHANNELS,
-    MAX_ACTOR_GROUPS, PERCEIVE_MAX_DELAY, SCRIPTED_VERSION, ...);
+    MAX_ACTOR_GROUPS, PERCEIVE_MAX_DELAY, ACTUATE_MAX_LEVELS, ESTIMATE_MAX_DELAY, ...);
   - every `typedef struct vss_<name>` is a ctypes.Structure in camel case with "IO" for "io" (vss_params -> VssParams,
-    vss_step_io -> VssStepIO, vss_actor_groups -> VssActorGroups, ...), pointer members as c_void_p;
+    vss_step_io -> VssStepIO, vss_actuate_params -> VssActuateParams, ...), pointer members as c_void_p;
   - EXPORTED is the prototypes' names and bind() sets their restype / argtypes on a library.
 The files the library's source stamp covers are likewise read from csrc/Makefile's STAMPED line.
 """
@@ -56,65 +56,14 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "vss.h"
 REBUILD = "`make -C {csrc}` or `python -c 'import __graft_entry__ as g; g.build()'`"
 
 
-# ---- the stamp and the loader, once: this module, actuate.py and estimate.py wrap them with their own globals ----
-def read_stamped(csrc: str) -> tuple:
-    """The files `csrc`/Makefile stamps into its library, in its order: the words of its STAMPED line, each without
+def _stamped() -> tuple:
+    """The files csrc/Makefile stamps into libvss_amd.so, in its order: the words of its STAMPED line, each without
     the ":<flag set>" a translation unit carries there."""
-    with open(os.path.join(csrc, "Makefile")) as f:
+    with open(os.path.join(CSRC, "Makefile")) as f:
         line = re.search(r"^STAMPED\s*:?=\s*(\S.*)$", f.read(), re.M)
     if not line:
-        raise NativeError(f"{csrc}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
-    return tuple(os.path.normpath(os.path.join(csrc, word.split(":")[0])) for word in line.group(1).split())
-
-
-def hash_files(paths) -> str:
-    """sha256 (first 16 hex digits) of the files' bytes, in order."""
-    h = hashlib.sha256()
-    for path in paths:
-        with open(path, "rb") as f:
-            h.update(f.read())
-    return h.hexdigest()[:16]
-
-
-def check_stamp(lib, symbol: str, want: str, lib_path: str) -> None:
-    """Raise unless `lib`'s `symbol`() returns `want` (a stale prebuilt .so, or one older than the stamp)."""
-    try:
-        fn = getattr(lib, symbol)
-    except AttributeError:  # a library older than the stamp: stale by definition
-        built = f"<no {symbol} symbol>"
-    else:
-        fn.restype = ctypes.c_char_p
-        built = fn().decode()
-    if built != want:
-        raise NativeError(f"{lib_path} was built from other sources (stamp {built}, tree {want}); rebuild it with "
-                          + REBUILD.format(csrc=CSRC))
-
-
-def bind_abi(lib: ctypes.CDLL, abi, header: str) -> ctypes.CDLL:
-    try:
-        return cheader.bind(lib, abi)
-    except AttributeError as e:
-        raise NativeError(f"{getattr(lib, '_name', lib)} lacks an entry point that {header} declares: {e}") from None
-
-
-def load_stamped(name: str, noun: str, lib_path: str, verify, abi, header: str, version_fn: str, version: int) -> ctypes.CDLL:
-    """Load the library `name` (the VSS `noun` library) from `lib_path`: raises if it has not been built, if
-    `verify(lib)` refuses its source stamp, if it lacks an entry point of `header`, or if its `version_fn`() is not
-    `version`."""
-    if not os.path.exists(lib_path):
-        raise NativeError(f"VSS {noun} library not found at {lib_path}; build it with " + REBUILD.format(csrc=CSRC))
-    L = ctypes.CDLL(lib_path)
-    verify(L)
-    bind_abi(L, abi, header)
-    built = getattr(L, version_fn)()
-    if built != version:
-        raise NativeError(f"{name} ABI {built} != expected {version}")
-    return L
-
-
-def _stamped() -> tuple:
-    """The files csrc/Makefile stamps into libvss_amd.so, in its order."""
-    return read_stamped(CSRC)
+        raise NativeError(f"{CSRC}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
+    return tuple(os.path.normpath(os.path.join(CSRC, word.split(":")[0])) for word in line.group(1).split())
 
 
 STAMPED = _stamped()
@@ -131,25 +80,52 @@ _lib = None
 
 def source_hash() -> str:
     """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
-    return hash_files(STAMPED)
+    h = hashlib.sha256()
+    for path in STAMPED:
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
 
 
 def verify_source_hash(lib: ctypes.CDLL, expected: str | None = None) -> None:
-    """Raise unless the library was built from the tree's sources (a stale prebuilt .so)."""
-    check_stamp(lib, "vss_source_hash", source_hash() if expected is None else expected, LIB_PATH)
+    """Raise unless the library was built from the tree's sources (a stale prebuilt .so, or one older than the
+    stamp)."""
+    want = source_hash() if expected is None else expected
+    try:
+        fn = lib.vss_source_hash
+    except AttributeError:  # a library older than the stamp: stale by definition
+        built = "<no vss_source_hash symbol>"
+    else:
+        fn.restype = ctypes.c_char_p
+        built = fn().decode()
+    if built != want:
+        raise NativeError(f"{LIB_PATH} was built from other sources (stamp {built}, tree {want}); rebuild it with "
+                          + REBUILD.format(csrc=CSRC))
 
 
 def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     """Set the header's restype / argtypes on `lib` (this library, or a variant build of the same ABI)."""
-    return bind_abi(lib, ABI, HEADER)
+    try:
+        return cheader.bind(lib, ABI)
+    except AttributeError as e:
+        raise NativeError(f"{getattr(lib, '_name', lib)} lacks an entry point that {HEADER} declares: {e}") from None
 
 
 def load() -> ctypes.CDLL:
     """Load libvss_amd.so (raises if it has not been built, or was built from other sources)."""
     global _lib
-    if _lib is None:
-        _lib = load_stamped("libvss_amd", "HIP", LIB_PATH, verify_source_hash, ABI, HEADER, "vss_abi_version", ABI_VERSION)
-    return _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise NativeError(f"VSS HIP library not found at {LIB_PATH}; build it with " + REBUILD.format(csrc=CSRC))
+    L = ctypes.CDLL(LIB_PATH)
+    verify_source_hash(L)
+    bind(L)
+    built = L.vss_abi_version()
+    if built != ABI_VERSION:
+        raise NativeError(f"libvss_amd ABI {built} != expected {ABI_VERSION}")
+    _lib = L
+    return L
 
 
 def check(rc: int, what: str) -> None:

@@ -1,4 +1,4 @@
-"""The actuation channel (include/vss_actuate.h `vss_actuate`, csrc/actuate/vss_actuate.hip).
+"""The actuation channel (include/vss.h `vss_actuate`, csrc/vss_actuate.hip).
 
 What a policy commands does not reach a real VSS robot's wheels exactly: the radio carries a command in [-1, 1] in a
 few bits, a packet is lost now and then (the robot keeps the command it had), small commands do not move a wheel,
@@ -22,20 +22,18 @@ A command is the two floats (left wheel, right wheel) of one robot.  Per call (i
   m = |r| < deadband ? 0 : r;  out = m * G + noise_sigma * zn[i]
   held' = r;  gain' = G;  episode' = episode + fresh
 zn: 12 unit normals of the counter (f, t, 8 << 24, block 0..2); zg: of (f, episode', 9 << 24, block); lost[T]: word
-T of block 3 of the step's counter.  The library is a second one, libvss_actuate.so, loaded here: include/vss.h and
-libvss_amd.so stay exactly as they are.
+T of block 3 of the step's counter.
 """
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import NamedTuple
 
 import numpy as np
-import torch  # noqa: F401  (loads torch's HIP runtime before the library resolves it, as vss_amd/_native.py)
+import torch
 
 from . import _native as N
-from . import channel, cheader
+from . import channel
 from .perceive import _box_muller, _philox, _u01
 
 F = np.float32
@@ -46,51 +44,14 @@ PURPOSE_EPISODE = 9   # ... of the per-episode draws
 LOSS_BLOCK = 3
 DRAWS = 12            # unit normals per (field, call) and per (field, episode): two per entity
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libvss_actuate.so")
-CSRC = os.path.join(N.CSRC, "actuate")
-HEADER = os.path.join(os.path.dirname(N.HEADER), "vss_actuate.h")
-
-
-def _stamped() -> tuple:
-    """The files csrc/actuate/Makefile stamps into the library, in its order (as _native._stamped for the core)."""
-    return N.read_stamped(CSRC)
-
-
-STAMPED = _stamped()
-
-with open(HEADER) as _f:
-    ABI = cheader.parse(_f.read())
-EXPORTED = tuple(ABI.functions)
-ABI_VERSION = ABI.constants["VSS_ACTUATE_ABI_VERSION"]
-MAX_LEVELS = ABI.constants["VSS_ACTUATE_MAX_LEVELS"]
-VssActuateLayout = ABI.structs["vss_actuate_layout"]
-VssActuateParams = ABI.structs["vss_actuate_params"]
-
-_lib = None
-
-
-def source_hash() -> str:
-    """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
-    return N.hash_files(STAMPED)
-
-
-def verify_source_hash(lib, expected: str | None = None) -> None:
-    """Raise unless the library was built from the tree's sources (a stale prebuilt .so)."""
-    N.check_stamp(lib, "vss_actuate_source_hash", source_hash() if expected is None else expected, LIB_PATH)
-
-
-def load() -> ctypes.CDLL:
-    """Load libvss_actuate.so (raises if it has not been built, or was built from other sources)."""
-    global _lib
-    if _lib is None:
-        _lib = N.load_stamped("libvss_actuate", "actuation", LIB_PATH, verify_source_hash, ABI, HEADER,
-                              "vss_actuate_abi_version", ABI_VERSION)
-    return _lib
+MAX_LEVELS = N.ACTUATE_MAX_LEVELS
+VssActuateLayout = N.VssActuateLayout
+VssActuateParams = N.VssActuateParams
+load = N.load  # the one library's loader under the module's own name, as before
 
 
 class Layout(NamedTuple):
-    """Where the commands lie (include/vss_actuate.h vss_actuate_layout), strides in robots (2 floats)."""
+    """Where the commands lie (include/vss.h vss_actuate_layout), strides in robots (2 floats)."""
     field_stride: int
     team_stride: int = 0
     robots: int = 1
@@ -276,7 +237,6 @@ class ActuationChannel(channel.Channel):
     def __init__(self, n_fields: int, layout, params=Params(), seed: int = 0, device="cuda", done_stride: int = 1,
                  rows: int | None = None):
         self.device = N.require_device(device)
-        load()
         self.n_fields, self.layout, self.params = int(n_fields), Layout(*layout), Params(*params).check()
         self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self.done_stride = int(done_stride)
@@ -323,7 +283,7 @@ class ActuationChannel(channel.Channel):
                 raise ValueError(f"done_prev must be contiguous int64 with a flag every {self.done_stride} elements for "
                                  f"{self.n_fields} fields (start() makes the next call a start call)")
             done_ptr = done_prev.data_ptr()
-        rc = load().vss_actuate(N.stream_of(self.device), self.n_fields, ctypes.byref(self._lay), ctypes.byref(self._prm),
+        rc = N.load().vss_actuate(N.stream_of(self.device), self.n_fields, ctypes.byref(self._lay), ctypes.byref(self._prm),
                                 self.seed, self.call & 0xFFFFFFFF, cmd.data_ptr(), done_ptr, self.done_stride,
                                 self.held.data_ptr(), self.gain.data_ptr(), self.episode.data_ptr(), dst.data_ptr())
         N.check(rc, "vss_actuate")

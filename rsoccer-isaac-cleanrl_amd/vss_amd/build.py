@@ -1,4 +1,4 @@
-"""Build libvss_amd.so, libvss_actuate.so and libvss_estimate.so for gfx950 (hipcc cross-compiles; no GPU needed)."""
+"""Build libvss_amd.so for gfx950 (hipcc cross-compiles; no GPU needed)."""
 from __future__ import annotations
 
 import os
@@ -14,8 +14,6 @@ def build(arch: str = "gfx950", verbose: bool = False) -> str:
     if not verbose:
         cmd.insert(1, "-s")
     subprocess.run(cmd, check=True)
-    # the second and the third one: csrc/actuate and csrc/estimate, by the same make
-    for lib in (out, os.path.join(HERE, "libvss_actuate.so"), os.path.join(HERE, "libvss_estimate.so")):
-        if not os.path.exists(lib):
-            raise RuntimeError(f"build did not produce {lib}")
+    if not os.path.exists(out):
+        raise RuntimeError(f"build did not produce {out}")
     return out

@@ -1,4 +1,4 @@
-"""The estimation channel (include/vss_estimate.h `vss_estimate`, csrc/estimate/vss_estimate.hip).
+"""The estimation channel (include/vss.h `vss_estimate`, csrc/vss_estimate.hip).
 
 A real VSS team never feeds late camera frames to its controller: it rolls every frame forward by the known latency
 with a motion model, which it can do because it knows what it commanded in the meantime.  The perception channel
@@ -25,20 +25,18 @@ floats, the floats of call t in slot t % delay.  Per call (index t) and row, wit
   hist[t % delay] = obs's own-action floats
 A lead is at most the number of calls since the episode's first, so the oldest slot read was written by the episode's
 second call: no command of an earlier episode is ever used.  There are no contacts and no walls: a body that would
-have hit something is predicted through it.  The library is a third one, libvss_estimate.so, loaded here:
-include/vss.h, libvss_amd.so and libvss_actuate.so stay exactly as they are.
+have hit something is predicted through it.
 """
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import NamedTuple
 
 import numpy as np
-import torch  # noqa: F401  (loads torch's HIP runtime before the library resolves it, as vss_amd/_native.py)
+import torch
 
 from . import _native as N
-from . import channel, cheader
+from . import channel
 from . import perceive as _P
 from .perceive import ACTION_FLOATS, NUM_OBS, _sincos_small
 
@@ -47,50 +45,13 @@ OWN = (4, 13, 22)        # where own robot j's nine floats begin
 OPPONENTS = (31, 38, 45)  # where opponent j's seven floats begin
 NSUB = 2                 # substeps per control step, of h = 0.025 s
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "libvss_estimate.so")
-CSRC = os.path.join(N.CSRC, "estimate")
-HEADER = os.path.join(os.path.dirname(N.HEADER), "vss_estimate.h")
-
-
-def _stamped() -> tuple:
-    """The files csrc/estimate/Makefile stamps into the library, in its order (as _native._stamped for the core)."""
-    return N.read_stamped(CSRC)
-
-
-STAMPED = _stamped()
-
-with open(HEADER) as _f:
-    ABI = cheader.parse(_f.read())
-EXPORTED = tuple(ABI.functions)
-ABI_VERSION = ABI.constants["VSS_ESTIMATE_ABI_VERSION"]
-MAX_DELAY = ABI.constants["VSS_ESTIMATE_MAX_DELAY"]
-VssEstimateLayout = ABI.structs["vss_estimate_layout"]
-
-_lib = None
-
-
-def source_hash() -> str:
-    """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
-    return N.hash_files(STAMPED)
-
-
-def verify_source_hash(lib, expected: str | None = None) -> None:
-    """Raise unless the library was built from the tree's sources (a stale prebuilt .so)."""
-    N.check_stamp(lib, "vss_estimate_source_hash", source_hash() if expected is None else expected, LIB_PATH)
-
-
-def load() -> ctypes.CDLL:
-    """Load libvss_estimate.so (raises if it has not been built, or was built from other sources)."""
-    global _lib
-    if _lib is None:
-        _lib = N.load_stamped("libvss_estimate", "estimation", LIB_PATH, verify_source_hash, ABI, HEADER,
-                              "vss_estimate_abi_version", ABI_VERSION)
-    return _lib
+MAX_DELAY = N.ESTIMATE_MAX_DELAY
+VssEstimateLayout = N.VssEstimateLayout
+load = N.load  # the one library's loader under the module's own name, as before
 
 
 class Layout(NamedTuple):
-    """Where the rows lie (include/vss_estimate.h vss_estimate_layout), strides in 52-float rows: perception's
+    """Where the rows lie (include/vss.h vss_estimate_layout), strides in 52-float rows: perception's
     layout without first_team -- a row is estimated in its own frame, whichever team's it is."""
     field_stride: int
     team_stride: int = 0
@@ -268,7 +229,6 @@ class EstimationChannel(channel.Channel):
 
     def __init__(self, n_fields: int, layout, delay: int = 0, device="cuda", done_stride: int = 1, rows: int | None = None):
         self.device = N.require_device(device)
-        load()
         self.n_fields, self.layout, self.delay = int(n_fields), Layout(*layout), int(delay)
         self.done_stride = int(done_stride)
         if not 0 <= self.delay <= MAX_DELAY:
@@ -285,7 +245,7 @@ class EstimationChannel(channel.Channel):
         self._lay = VssEstimateLayout(int(lay.field_stride), int(lay.team_stride), int(lay.robots), int(lay.n_teams))
 
     def _launch(self, obs, term, done) -> None:
-        rc = load().vss_estimate(
+        rc = N.load().vss_estimate(
             N.stream_of(self.device), self.n_fields, ctypes.byref(self._lay), self.delay, self.call & 0xFFFFFFFF,
             obs.data_ptr(), N.ptr(term), done.data_ptr(), self.done_stride,
             self.hist.data_ptr() if self.delay else None, self.age.data_ptr(), self.obs_out.data_ptr(),

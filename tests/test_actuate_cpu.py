@@ -1,5 +1,5 @@
-"""The actuation channel without a GPU (include/vss_actuate.h, vss_amd/actuate.py): the second
-library's ABI (3 functions, 2 structs, its own source stamp) beside an unchanged core, the entry's argument checks on
+"""The actuation channel without a GPU (include/vss.h, vss_amd/actuate.py): its part of the
+one ABI (1 function, 2 structs) and of the one library's source stamp, the entry's argument checks on
 addresses that are never dereferenced, the float32 specification `reference_actuate` on known answers, the statistics
 of its draws, and the flags' plumbing (parse_args, the checkpoint's structural keys)."""
 import ctypes
@@ -28,7 +28,7 @@ def call(n_fields=64, lay=(3, 0, 3, 1, 0), prm=(0.0, 0.0, 0.0, 0.0, 0), seed=1, 
          done_stride=1, held=FAKE + 2 * GAP, gain=FAKE + 3 * GAP, episode=FAKE + 4 * GAP, out=FAKE + 5 * GAP,
          null_lay=False, null_prm=False):
     layout, params = A.VssActuateLayout(*lay), A.VssActuateParams(*prm)
-    return A.load().vss_actuate(None, n_fields, None if null_lay else ctypes.byref(layout),
+    return N.load().vss_actuate(None, n_fields, None if null_lay else ctypes.byref(layout),
                                 None if null_prm else ctypes.byref(params), seed, call_index, cmd, done, done_stride, held,
                                 gain, episode, out)
 
@@ -67,63 +67,62 @@ def done_patterns(calls, n):
     return np.ascontiguousarray(d[:, :n]) if n >= 5 else np.ascontiguousarray(d[:, [3, 2, 1, 4, 0][:n]])
 
 
-# ---- the second library's ABI, and the core's left as it was ---------------------------------------------------------
+# ---- the channel's part of the one ABI and the one library -------------------------------------------------------------
 def exported(path, prefix):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return sorted(m.group(1) for m in re.finditer(rf"^\S+\s+T\s+({prefix}\w*)$", out, flags=re.M))
 
 
-def test_the_header_is_three_functions_and_two_structs_and_the_library_exports_exactly_those():
-    with open(A.HEADER) as f:
-        h = cheader.parse(f.read())
-    assert sorted(h.functions) == ["vss_actuate", "vss_actuate_abi_version", "vss_actuate_source_hash"] == sorted(A.EXPORTED)
-    assert sorted(h.structs) == ["vss_actuate_layout", "vss_actuate_params"]
-    assert h.constants["VSS_ACTUATE_ABI_VERSION"] == 1 and h.constants["VSS_ACTUATE_MAX_LEVELS"] == 32767 == A.MAX_LEVELS
-    lib = A.load()
-    assert lib.vss_actuate_abi_version() == 1 == A.ABI_VERSION
-    assert ctypes.sizeof(A.VssActuateLayout) == 32 and ctypes.sizeof(A.VssActuateParams) == 20
-    if shutil.which("nm"):
-        assert exported(A.LIB_PATH, "vss_") == sorted(h.functions)
-
-
-def test_the_core_header_and_library_are_as_they_were():
+def test_the_header_declares_vss_actuate_and_its_two_structs_and_the_library_exports_it():
     with open(N.HEADER) as f:
         h = cheader.parse(f.read())
-    assert len(h.functions) == 61 and len(h.structs) == 10
-    assert not any("actuate" in name for name in list(h.functions) + list(h.structs) + list(N.EXPORTED))
-    assert not any("actuate" in p for p in N.STAMPED)
+    assert [name for name in h.functions if "actuate" in name] == ["vss_actuate"] and "vss_actuate" in N.EXPORTED
+    assert sorted(name for name in h.structs if "actuate" in name) == ["vss_actuate_layout", "vss_actuate_params"]
+    assert {k: v for k, v in h.constants.items() if "ACTUATE" in k} == {"VSS_ACTUATE_MAX_LEVELS": 32767}
+    assert A.MAX_LEVELS == 32767 == N.ACTUATE_MAX_LEVELS
+    assert A.VssActuateLayout is N.VssActuateLayout and A.VssActuateParams is N.VssActuateParams
+    assert ctypes.sizeof(A.VssActuateLayout) == 32 and ctypes.sizeof(A.VssActuateParams) == 20
+    assert ctypes.sizeof(h.structs["vss_actuate_layout"]) == 32 and ctypes.sizeof(h.structs["vss_actuate_params"]) == 20
+    assert N.load().vss_actuate.argtypes == h.functions["vss_actuate"][1]
     if shutil.which("nm"):
+        assert exported(N.LIB_PATH, "vss_actuate") == ["vss_actuate"]
         assert exported(N.LIB_PATH, "vss_") == sorted(h.functions)
 
 
+def test_the_unit_is_one_of_the_core_librarys_and_nothing_is_packaged_beside_it():
+    assert [os.path.basename(p) for p in N.STAMPED].count("vss_actuate.hip") == 1
+    assert os.path.join(N.CSRC, "vss_actuate.hip") in N.STAMPED
+    assert [os.path.join(d, f) for d, _, files in os.walk(N.CSRC) for f in files if f == "Makefile" or f.endswith(".mk")] \
+        == [os.path.join(N.CSRC, "Makefile")]
+    for name in ("LIB_PATH", "STAMPED", "CSRC", "HEADER", "ABI", "EXPORTED", "ABI_VERSION", "source_hash", "verify_source_hash"):
+        assert not hasattr(A, name), name
+    assert A.load is N.load  # the module's own name for the one loader
+    assert not os.path.exists(os.path.join(os.path.dirname(N.HEADER), "vss_actuate.h"))
+
+
 def test_the_stamp_covers_the_makefiles_list_and_a_stale_library_is_refused_at_load(tmp_path, monkeypatch):
-    with open(os.path.join(A.CSRC, "Makefile")) as f:
+    """A library built before vss_actuate.hip was edited is refused, and the hash a state file records
+    (checkpoint.source_hash is N.source_hash) changes with that edit."""
+    with open(os.path.join(N.CSRC, "Makefile")) as f:
         (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
-    assert line.split() == ["vss_actuate.hip:STEP_FLAGS", "../vss_numerics.h", "../../../include/vss_actuate.h", "../../../include/vss.h",
-                            "Makefile", "../stamped.mk"]
-    assert [os.path.basename(p) for p in A.STAMPED] == ["vss_actuate.hip", "vss_numerics.h", "vss_actuate.h", "vss.h", "Makefile",
-                                                        "stamped.mk"]
-    assert A.HEADER in A.STAMPED and N.HEADER in A.STAMPED and all(os.path.isfile(p) for p in A.STAMPED)
-    lib = A.load()
-    A.verify_source_hash(lib)
+    assert "vss_actuate.hip:STEP_FLAGS" in line.split()
+    at = list(N.STAMPED).index(os.path.join(N.CSRC, "vss_actuate.hip"))
+    assert all(os.path.isfile(p) for p in N.STAMPED)
+    lib = N.load()
+    N.verify_source_hash(lib)
     with pytest.raises(N.NativeError, match="built from other sources"):
-        A.verify_source_hash(lib, expected="0" * 16)
+        N.verify_source_hash(lib, expected="0" * 16)
+    before = N.source_hash()
+    assert CK.source_hash() == before
     src = os.path.join(tmp_path, "vss_actuate.hip")
-    shutil.copy(A.STAMPED[0], src)
+    shutil.copy(N.STAMPED[at], src)
     with open(src, "a") as f:
         f.write("// edited after the build\n")
-    monkeypatch.setattr(A, "STAMPED", (src,) + tuple(A.STAMPED[1:]))
-    monkeypatch.setattr(A, "_lib", None)
+    monkeypatch.setattr(N, "STAMPED", tuple(N.STAMPED[:at]) + (src,) + tuple(N.STAMPED[at + 1:]))
+    monkeypatch.setattr(N, "_lib", None)
     with pytest.raises(N.NativeError, match=r"built from other sources.*make -C"):
-        A.load()
-
-
-def test_a_library_without_the_stamp_symbol_is_refused():
-    class NoStamp:
-        def __getattr__(self, name):
-            raise AttributeError(name)
-    with pytest.raises(N.NativeError, match="make -C"):
-        A.verify_source_hash(NoStamp())
+        N.load()
+    assert N.source_hash() != before and CK.source_hash() == N.source_hash()
 
 
 # ---- the entry's refusals ----------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""vss_actuate on the GPU (csrc/actuate/vss_actuate.hip): the kernel equals
+"""vss_actuate on the GPU (csrc/vss_actuate.hip): the kernel equals
 vss_amd.actuate.reference_actuate bit for bit -- out, held, gain and episode after every one of 12 calls, for every layout
 a wrapper uses, every effect off, alone and all on -- writes nothing outside its commands, works in place, honours a
 hand-set gain, and the Actuated wrapper's closed loop on a DMA env (goals, time-outs, resets) is the reference fed with
@@ -94,7 +94,7 @@ def run_case(n, layout, done_stride, params, seed, in_place=False, set_gain_at=N
     done_b = Buf((n - 1) * done_stride + 1, 1, torch.long)
     c_lay, c_prm = A.VssActuateLayout(*lay), A.VssActuateParams(*params)
     held, gain, episode = np.zeros(shape, F32), np.ones(shape, F32), np.zeros(n, np.uint32)
-    lib, stream = A.load(), N.stream_of(torch.device(DEV))
+    lib, stream = N.load(), N.stream_of(torch.device(DEV))
     for t in range(CALLS):
         cmd = commands(g, shape)
         start = t == 0
@@ -203,7 +203,7 @@ def test_the_bindings_refusals():
     assert ch.call == 1
     bad = A.VssActuateLayout(1, 0, 2, 1, 0)
     prm = A.VssActuateParams(0, 0, 0, 0, 0)
-    rc = A.load().vss_actuate(N.stream_of(torch.device(DEV)), n, ctypes.byref(bad), ctypes.byref(prm), 1, 0, cmd.data_ptr(),
+    rc = N.load().vss_actuate(N.stream_of(torch.device(DEV)), n, ctypes.byref(bad), ctypes.byref(prm), 1, 0, cmd.data_ptr(),
                               None, 1, ch.held.data_ptr(), ch.gain.data_ptr(), ch.episode.data_ptr(), ch.out.data_ptr())
     assert rc == 1
 

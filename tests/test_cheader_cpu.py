@@ -141,7 +141,7 @@ def test_the_loaded_library_carries_the_headers_types():
     """load() binds through bind(): every entry point of the loaded library has the parsed restype and argtypes, a
     pointer never an integer slot, and the modules' names are the header's values."""
     lib = N.load()
-    assert len(N.ABI.functions) == 61 and tuple(N.ABI.functions) == N.EXPORTED
+    assert len(N.ABI.functions) == 63 and tuple(N.ABI.functions) == N.EXPORTED
     for name, (restype, argtypes) in N.ABI.functions.items():
         fn = getattr(lib, name)
         assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
@@ -157,7 +157,9 @@ def test_the_loaded_library_carries_the_headers_types():
     structs = {"vss_params": N.VssParams, "vss_state": N.VssState, "vss_step_io": N.VssStepIO,
                "vss_rollout_io": N.VssRolloutIO, "vss_replay_draws": N.VssReplayDraws, "vss_versus_io": N.VssVersusIO,
                "vss_mirror_io": N.VssMirrorIO, "vss_actor_groups": N.VssActorGroups,
-               "vss_perceive_layout": N.VssPerceiveLayout, "vss_perceive_noise": N.VssPerceiveNoise}
+               "vss_perceive_layout": N.VssPerceiveLayout, "vss_perceive_noise": N.VssPerceiveNoise,
+               "vss_actuate_layout": N.VssActuateLayout, "vss_actuate_params": N.VssActuateParams,
+               "vss_estimate_layout": N.VssEstimateLayout}
     assert structs == N.ABI.structs
 
 
@@ -181,7 +183,7 @@ def test_struct_layouts_equal_the_c_compilers(tmp_path):
     subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.dirname(N.HEADER), "-o", str(exe), str(src)],
                    check=True, capture_output=True, text=True)
     got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")[:-1]
-    assert len(N.ABI.structs) == 10 and got == want
+    assert len(N.ABI.structs) == 13 and got == want
 
 
 def test_the_oracles_mirrors_equal_the_derived_ones():

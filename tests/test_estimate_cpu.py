@@ -1,5 +1,5 @@
-"""The estimation channel without a GPU (include/vss_estimate.h, vss_amd/estimate.py): the third
-library's ABI (3 functions, 1 struct, its own source stamp) beside an unchanged core and actuation library, the entry's
+"""The estimation channel without a GPU (include/vss.h, vss_amd/estimate.py): its part of the
+one ABI (1 function, 1 struct) and of the one library's source stamp, the entry's
 argument checks on addresses that are never dereferenced, the float32 specification `reference_estimate` on known
 answers -- DESIGN.md §3's table, the episode edges, one world -- and against the project's own physics (the C oracle)
 on contact-free scenes, and the flag's plumbing (parse_args, the checkpoint's structural key)."""
@@ -16,7 +16,6 @@ import oracle as O
 import ppo_continuous_action_isaacgym as P
 from test_perceive_cpu import done_patterns, same_bits, world
 from vss_amd import _native as N
-from vss_amd import actuate as A
 from vss_amd import checkpoint as CK
 from vss_amd import cheader
 from vss_amd import estimate as E
@@ -34,7 +33,7 @@ def call(n_fields=64, lay=(3, 0, 3, 1), delay=2, call_index=0, obs=FAKE, term=FA
          done_stride=1, hist=FAKE + 3 * GAP, age=FAKE + 5 * GAP, obs_out=FAKE + 6 * GAP, term_out=FAKE + 7 * GAP,
          null_lay=False):
     layout = E.VssEstimateLayout(*lay)
-    return E.load().vss_estimate(None, n_fields, None if null_lay else ctypes.byref(layout), delay, call_index, obs, term,
+    return N.load().vss_estimate(None, n_fields, None if null_lay else ctypes.byref(layout), delay, call_index, obs, term,
                                  done, done_stride, hist, age, obs_out, term_out)
 
 
@@ -60,67 +59,61 @@ def rest_rows(m, yaw=0.0):
     return rows
 
 
-# ---- the third library's ABI, and the other two left as they were ------------------------------------------------------
+# ---- the channel's part of the one ABI and the one library -------------------------------------------------------------
 def exported(path, prefix):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return sorted(m.group(1) for m in re.finditer(rf"^\S+\s+T\s+({prefix}\w*)$", out, flags=re.M))
 
 
-def test_the_header_is_three_functions_and_one_struct_and_the_library_exports_exactly_those():
-    with open(E.HEADER) as f:
-        h = cheader.parse(f.read())
-    assert sorted(h.functions) == ["vss_estimate", "vss_estimate_abi_version", "vss_estimate_source_hash"] == sorted(E.EXPORTED)
-    assert sorted(h.structs) == ["vss_estimate_layout"]
-    assert h.constants["VSS_ESTIMATE_ABI_VERSION"] == 1 and h.constants["VSS_ESTIMATE_MAX_DELAY"] == 15 == E.MAX_DELAY
-    lib = E.load()
-    assert lib.vss_estimate_abi_version() == 1 == E.ABI_VERSION
-    assert ctypes.sizeof(E.VssEstimateLayout) == 24
-    if shutil.which("nm"):
-        assert exported(E.LIB_PATH, "vss_") == sorted(h.functions)
-
-
-def test_the_core_header_and_the_other_libraries_stamps_are_as_they_were():
+def test_the_header_declares_vss_estimate_and_its_struct_and_the_library_exports_it():
     with open(N.HEADER) as f:
         h = cheader.parse(f.read())
-    assert len(h.functions) == 61 and len(h.structs) == 10
-    assert not any("estimate" in name for name in list(h.functions) + list(h.structs) + list(N.EXPORTED))
-    assert not any("estimate" in p for p in N.STAMPED + A.STAMPED)
-    assert [os.path.basename(p) for p in A.STAMPED] == ["vss_actuate.hip", "vss_numerics.h", "vss_actuate.h", "vss.h", "Makefile",
-                                                        "stamped.mk"]
-    assert [os.path.basename(p) for p in N.STAMPED] == [
-        "vss_step.hip", "vss_update.hip", "vss_policy.hip", "vss_gemm_x6.hip", "vss_loss.hip", "vss_optim.hip",
-        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_loss_row.h", "vss_numerics.h", "vss.h", "Makefile",
-        "stamped.mk"]
+    assert [name for name in h.functions if "estimate" in name] == ["vss_estimate"] and "vss_estimate" in N.EXPORTED
+    assert sorted(name for name in h.structs if "estimate" in name) == ["vss_estimate_layout"]
+    assert {k: v for k, v in h.constants.items() if "ESTIMATE" in k} == {"VSS_ESTIMATE_MAX_DELAY": 15}
+    assert E.MAX_DELAY == 15 == N.ESTIMATE_MAX_DELAY
+    assert E.VssEstimateLayout is N.VssEstimateLayout
+    assert ctypes.sizeof(E.VssEstimateLayout) == 24 == ctypes.sizeof(h.structs["vss_estimate_layout"])
+    assert N.load().vss_estimate.argtypes == h.functions["vss_estimate"][1]
     if shutil.which("nm"):
+        assert exported(N.LIB_PATH, "vss_estimate") == ["vss_estimate"]
         assert exported(N.LIB_PATH, "vss_") == sorted(h.functions)
 
 
+def test_the_unit_is_one_of_the_core_librarys_and_nothing_is_packaged_beside_it():
+    assert [os.path.basename(p) for p in N.STAMPED].count("vss_estimate.hip") == 1
+    assert os.path.join(N.CSRC, "vss_estimate.hip") in N.STAMPED
+    assert [os.path.join(d, f) for d, _, files in os.walk(N.CSRC) for f in files if f == "Makefile" or f.endswith(".mk")] \
+        == [os.path.join(N.CSRC, "Makefile")]
+    for name in ("LIB_PATH", "STAMPED", "CSRC", "HEADER", "ABI", "EXPORTED", "ABI_VERSION", "source_hash", "verify_source_hash"):
+        assert not hasattr(E, name), name
+    assert E.load is N.load  # the module's own name for the one loader
+    assert not os.path.exists(os.path.join(os.path.dirname(N.HEADER), "vss_estimate.h"))
+
+
 def test_the_stamp_covers_the_makefiles_list_and_a_stale_library_is_refused_at_load(tmp_path, monkeypatch):
-    with open(os.path.join(E.CSRC, "Makefile")) as f:
+    """A library built before vss_estimate.hip was edited is refused, and the hash a state file records
+    (checkpoint.source_hash is N.source_hash) changes with that edit."""
+    with open(os.path.join(N.CSRC, "Makefile")) as f:
         (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
-    assert line.split() == ["vss_estimate.hip:STEP_FLAGS", "../vss_numerics.h", "../../../include/vss_estimate.h", "../../../include/vss.h",
-                            "Makefile", "../stamped.mk"]
-    assert [os.path.basename(p) for p in E.STAMPED] == ["vss_estimate.hip", "vss_numerics.h", "vss_estimate.h", "vss.h", "Makefile",
-                                                        "stamped.mk"]
-    assert E.HEADER in E.STAMPED and N.HEADER in E.STAMPED and all(os.path.isfile(p) for p in E.STAMPED)
-    lib = E.load()
-    E.verify_source_hash(lib)
+    assert "vss_estimate.hip:STEP_FLAGS" in line.split()
+    at = list(N.STAMPED).index(os.path.join(N.CSRC, "vss_estimate.hip"))
+    assert all(os.path.isfile(p) for p in N.STAMPED)
+    lib = N.load()
+    N.verify_source_hash(lib)
     with pytest.raises(N.NativeError, match="built from other sources"):
-        E.verify_source_hash(lib, expected="0" * 16)
+        N.verify_source_hash(lib, expected="0" * 16)
+    before = N.source_hash()
+    assert CK.source_hash() == before
     src = os.path.join(tmp_path, "vss_estimate.hip")
-    shutil.copy(E.STAMPED[0], src)
+    shutil.copy(N.STAMPED[at], src)
     with open(src, "a") as f:
         f.write("// edited after the build\n")
-    monkeypatch.setattr(E, "STAMPED", (src,) + tuple(E.STAMPED[1:]))
-    monkeypatch.setattr(E, "_lib", None)
+    monkeypatch.setattr(N, "STAMPED", tuple(N.STAMPED[:at]) + (src,) + tuple(N.STAMPED[at + 1:]))
+    monkeypatch.setattr(N, "_lib", None)
     with pytest.raises(N.NativeError, match=r"built from other sources.*make -C"):
-        E.load()
-
-    class NoStamp:
-        def __getattr__(self, name):
-            raise AttributeError(name)
-    with pytest.raises(N.NativeError, match="make -C"):
-        E.verify_source_hash(NoStamp())
+        N.load()
+    assert N.source_hash() != before and CK.source_hash() == N.source_hash()
 
 
 # ---- the entry's refusals ----------------------------------------------------------------------------------------------

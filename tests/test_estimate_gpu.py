@@ -1,4 +1,4 @@
-"""vss_estimate on the GPU (csrc/estimate/vss_estimate.hip): the kernel equals
+"""vss_estimate on the GPU (csrc/vss_estimate.hip): the kernel equals
 vss_amd.estimate.reference_estimate bit for bit -- both outputs, the command ring and the ages after every one of 12
 calls, for every layout a wrapper uses, delays 0, 1, 3, 15 -- writes nothing outside its rows, and the Estimated
 wrapper's closed loop on a perceived DMA env (goals, time-outs, resets) is the reference fed with Perceived's outputs."""
@@ -67,7 +67,7 @@ def run_case(n, layout, done_stride, delay, seed, share=0.7):
     done_b = Rows((n - 1) * done_stride + 1, 1, torch.long)
     c_lay = E.VssEstimateLayout(*lay)
     hist, age = np.zeros((delay,) + shape + (6,), F32), np.zeros(shape, np.int32)
-    lib, stream = E.load(), N.stream_of(torch.device(DEV))
+    lib, stream = N.load(), N.stream_of(torch.device(DEV))
     for t in range(CALLS):
         obs = plausible_rows(g, shape)
         term = np.where((g.random(shape) < share)[..., None], obs, plausible_rows(g, shape))
@@ -173,7 +173,7 @@ def test_the_bindings_refusals():
         ch.estimate(ch.obs_out, obs, done)  # an output as an input: the entry's own refusal
     assert ch.call == 0
     bad = E.VssEstimateLayout(1, 0, 2, 1)
-    rc = E.load().vss_estimate(N.stream_of(torch.device(DEV)), n, ctypes.byref(bad), 1, 0, obs.data_ptr(), None,
+    rc = N.load().vss_estimate(N.stream_of(torch.device(DEV)), n, ctypes.byref(bad), 1, 0, obs.data_ptr(), None,
                                done.data_ptr(), 1, ch.hist.data_ptr(), ch.age.data_ptr(), ch.obs_out.data_ptr(), None)
     assert rc == 1
 

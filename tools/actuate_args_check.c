@@ -1,9 +1,9 @@
-/* Host-side argument validation of vss_actuate (include/vss_actuate.h) as a stand-alone program for ASan + UBSan.
+/* Host-side argument validation of vss_actuate (include/vss.h) as a stand-alone program for ASan + UBSan.
  * Every call below is rejected (or returns VSS_OK for a zero size) before any HIP call, so it runs on a
  * CPU-only machine; the pointers are fake, non-null and never dereferenced.  Build the host code of
  * vss_actuate.hip with the sanitizers and run (from the repository root):
  *
- *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc/actuate
+ *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc
  *   SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
  *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off $SAN -c $C/vss_actuate.hip -o $O/ac.o
  *   hipcc -fsanitize=address,undefined -fno-sanitize-recover=undefined -g -x c tools/actuate_args_check.c \
@@ -13,7 +13,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../include/vss_actuate.h"
+#include "../include/vss.h"
 
 static int failures = 0;
 #define EXPECT(call, want)                                                        \
@@ -51,7 +51,6 @@ static int run(call_args a) {
 
 int main(void) {
   call_args a;
-  EXPECT(vss_actuate_abi_version(), VSS_ACTUATE_ABI_VERSION);
   /* zero size: OK, no launch -- a step call, a start call, in place, two teams */
   a = good(); a.n = 0; EXPECT(run(a), VSS_OK);
   a = good(); a.n = 0; a.done = 0; EXPECT(run(a), VSS_OK);

@@ -1,9 +1,9 @@
-/* Host-side argument validation of vss_estimate (include/vss_estimate.h) as a stand-alone program for ASan + UBSan.
+/* Host-side argument validation of vss_estimate (include/vss.h) as a stand-alone program for ASan + UBSan.
  * Every call below is rejected (or returns VSS_OK for a zero size) before any HIP call, so it runs on a
  * CPU-only machine; the pointers are fake, non-null and never dereferenced.  Build the host code of
  * vss_estimate.hip with the sanitizers and run (from the repository root):
  *
- *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc/estimate
+ *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc
  *   SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
  *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off $SAN -c $C/vss_estimate.hip -o $O/es.o
  *   hipcc -fsanitize=address,undefined -fno-sanitize-recover=undefined -g -x c tools/estimate_args_check.c \
@@ -12,7 +12,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../include/vss_estimate.h"
+#include "../include/vss.h"
 
 static int failures = 0;
 #define EXPECT(call, want)                                                        \
@@ -51,7 +51,6 @@ static int run(call_args a) {
 
 int main(void) {
   call_args a;
-  EXPECT(vss_estimate_abi_version(), VSS_ESTIMATE_ABI_VERSION);
   /* zero size: OK, no launch -- a step call, a start call, two teams, no delay and no ring, the longest delay */
   a = good(); a.n = 0; EXPECT(run(a), VSS_OK);
   a = good(); a.n = 0; a.term = 0; a.term_out = 0; EXPECT(run(a), VSS_OK);
