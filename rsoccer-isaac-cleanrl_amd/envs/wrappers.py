@@ -75,6 +75,9 @@ def make_env(args):
     delay, noise = perception_args(args)
     if delay or noise.any():  # --obs-delay / --obs-noise-*: with all of them zero the chain is as without the flags
         wrapped = Perceived(wrapped, delay, noise, perception_seed(getattr(args, "seed", None)))
+    track = tracking_args(args)
+    if track.any():  # --obs-filter-*: round Perceived, inside Estimated; with every gain 0 the chain is as without the flags
+        wrapped = Tracked(wrapped, track)
     if estimation_args(args):  # --obs-predict 1: between Perceived and the policy; with 0 the chain is as without the flag
         wrapped = Estimated(wrapped)
     params = actuation_args(args)
@@ -124,10 +127,32 @@ def evaluation_estimation(args, env):
     return E.EstimationChannel(n, E.layout_full_blue(), perception_args(args)[0], env.device, rows=n * 6)
 
 
+def tracking_args(args):
+    """Params of --obs-filter-team / -opp / -ball / -gate-pos / -gate-vel; absent flags have their defaults (gains 0).
+    A gain without vision noise, or a value out of range, is refused (checkpoint.check_tracking)."""
+    from vss_amd.checkpoint import TRACKING_DEFAULTS, TRACKING_STRUCTURAL, check_tracking
+    from vss_amd.track import Params
+    check_tracking(args)
+    return Params(*(float(d if getattr(args, k, None) is None else getattr(args, k))
+                    for k, d in ((k, TRACKING_DEFAULTS[k]) for k in TRACKING_STRUCTURAL)))
+
+
+def evaluation_tracking(args, env):
+    """evaluate()'s tracking channel over the blue rows of the raw env's FULL layout (play.play_matches), applied
+    after the perception channel and before the estimation channel; None when every gain is 0."""
+    from vss_amd import track as T
+    params = tracking_args(args)
+    if not params.any():
+        return None
+    n = env.num_fields
+    return T.TrackingChannel(n, T.layout_full_blue(), perception_args(args)[0], params, env.device, rows=n * 6)
+
+
 def evaluation_kwargs(args, env) -> dict:
     """evaluate()'s channels as play.play_matches' keyword arguments; None for flags that are all zero."""
     perceive, actuate = evaluation_channels(args, env)
-    return dict(perceive=perceive, actuate=actuate, estimate=evaluation_estimation(args, env))
+    return dict(perceive=perceive, actuate=actuate, estimate=evaluation_estimation(args, env),
+                track=evaluation_tracking(args, env))
 
 
 def actuation_args(args):
@@ -365,7 +390,7 @@ class _ChannelTeam:
 
 
 class _ChannelWrapper(Wrapper):
-    """What Perceived, Estimated and Actuated share: a `channel` over the learner's rows or commands, an
+    """What Perceived, Tracked, Estimated and Actuated share: a `channel` over the learner's rows or commands, an
     `opponent_channel` (or None) over a policy opponent's, the inner wrapper's opponent buffers, and the checkpoint
     entries, labelled with the class's name."""
 
@@ -462,6 +487,79 @@ class Perceived(_ChannelWrapper):
 
 
 
+class _TrackedTeam(_ChannelTeam):
+    """Behind the yellow tracking channel: the team acts on the filtered opponent rows, whatever rows it is handed."""
+
+    def __call__(self, act, obs):
+        self.team(act, self.channel.obs_out.view(obs.shape))
+
+
+class Tracked(_ChannelWrapper):
+    """A recursive tracker round `Perceived` (vss_amd/track.py): `obs` and info["terminal_observation"]
+    become the perceived rows filtered across frames -- the last filtered row moved one step with the project's own
+    drive model, then corrected with the new row by a gain per kind of body behind a gate -- by one vss_track launch
+    per step, in the delayed frame's own time.  Rewards, dones and every other info pass through.  It goes round
+    Perceived and inside Estimated (filter, then dead-reckon to now) and Actuated.
+
+    Where Perceived puts a second channel in front of a policy opponent, a second tracking channel goes behind it,
+    exactly as Estimated's: it filters Perceived's opponent_channel.obs_out with the opponent layout, the same call
+    index and the same dones, and the team acts on its output.  The mirror wrappers get one two-team channel."""
+
+    def __init__(self, env, params):
+        if not isinstance(env, Perceived):
+            raise ValueError("Tracked goes round a Perceived wrapper: it filters what the perception channel delivers")
+        if not env.noise.any():
+            raise ValueError("Tracked goes round a Perceived wrapper with vision noise: with every sigma 0 there is "
+                             "nothing to filter")
+        super().__init__(env)
+        from vss_amd import track as T
+        self._base = env.env  # the SA / CMA / DMA or mirror wrapper
+        vss = self._base.env
+        self.delay, self.noise, self.params = env.delay, env.noise, T.Params(*params).check()
+        self.channel = T.TrackingChannel(vss.num_fields, T.of_perception(env.channel.layout), self.delay, self.params,
+                                         vss.device, done_stride=env.channel.done_stride)
+        self.opponent_channel = None
+        self.channel.start(env.channel.obs_out.view(self._base._obs.shape))  # as Perceived's constructor starts its own
+
+    def _perceived_opponent_rows(self):
+        return self.env.opponent_channel.obs_out.view(self.env._opp_obs.shape)
+
+    def set_opponent(self, team=None, perceived=None):
+        """Perceived's set_opponent; where that puts the yellow perception channel in front of the team (`perceived`,
+        default: a SnapshotOpponent or an OpponentPool), the yellow tracking channel goes behind it."""
+        from vss_amd import track as T
+        from vss_amd.opponent import OpponentPool, SnapshotOpponent
+        if perceived is None:
+            perceived = isinstance(team, (SnapshotOpponent, OpponentPool))
+        if team is None or not perceived:
+            self.env.set_opponent(team, perceived=False)
+            self.opponent_channel = None
+            return
+        vss = self._base.env
+        ch = T.TrackingChannel(vss.num_fields, T.layout_opponent(), self.delay, self.params, vss.device,
+                               done_stride=self.channel.done_stride)
+        self.env.set_opponent(_TrackedTeam(team, ch), perceived=True)
+        self.opponent_channel = ch
+        ch.start(self._perceived_opponent_rows(), call=max(self.channel.call - 1, 0))  # the learner's rows' last call
+
+    def reset(self, **kwargs):
+        obs = self.env.reset(**kwargs)["obs"]
+        if self.opponent_channel is not None:
+            self.opponent_channel.start(self._perceived_opponent_rows())
+        return {"obs": self.channel.start(obs)}
+
+    def step(self, action):
+        obs, reward, dones, infos = self.env.step(action)
+        f_obs, f_term = self.channel.track(obs["obs"], infos["terminal_observation"], dones)
+        if self.opponent_channel is not None:
+            # no terminal row on the yellow side: the perceived rows stand in and the second output is not used
+            rows = self._perceived_opponent_rows()
+            self.opponent_channel.track(rows, rows, dones)
+        infos = dict(infos, terminal_observation=f_term)
+        return {"obs": f_obs}, reward, dones, infos
+
+
+
 class _EstimatedTeam(_ChannelTeam):
     """Behind the yellow estimation channel: the team acts on the estimated opponent rows, whatever rows it is
     handed."""
@@ -474,19 +572,19 @@ class Estimated(_ChannelWrapper):
     """Dead reckoning round `Perceived` (vss_amd/estimate.py): `obs` and info["terminal_observation"]
     become the perceived rows rolled forward to the present -- by the rows' age, with the project's own drive model
     and the commands given in the meantime -- by one vss_estimate launch per step.  Rewards, dones and every other
-    info pass through.  It goes round Perceived and inside Actuated.
+    info pass through.  It goes round Perceived, or round Tracked(Perceived), and inside Actuated.
 
     Where Perceived puts a second channel in front of a policy opponent, a second estimation channel goes behind
     it: it estimates Perceived's opponent_channel.obs_out with the opponent layout, the same call index and the same
     dones, and the team acts on its output.  The mirror wrappers get one two-team channel."""
 
     def __init__(self, env):
-        if not isinstance(env, Perceived) or env.delay < 1:
+        if not isinstance(env, (Perceived, Tracked)) or env.delay < 1:
             raise ValueError("Estimated goes round a Perceived wrapper with a delay of at least 1: without latency there "
                              "is nothing to predict")
         super().__init__(env)
         from vss_amd import estimate as E
-        self._base = env.env  # the SA / CMA / DMA or mirror wrapper
+        self._base = env._base if isinstance(env, Tracked) else env.env  # the SA / CMA / DMA or mirror wrapper
         vss = self._base.env
         self.delay = env.delay
         self.channel = E.EstimationChannel(vss.num_fields, E.of_perception(env.channel.layout), self.delay, vss.device,
@@ -561,7 +659,7 @@ class Actuated(_ChannelWrapper):
         super().__init__(env)
         from vss_amd import actuate as A
         base = env
-        while isinstance(base, (Perceived, Estimated)):  # down to the SA / CMA / DMA or mirror wrapper
+        while isinstance(base, (Perceived, Tracked, Estimated)):  # down to the SA / CMA / DMA or mirror wrapper
             base = base.env
         vss = base.env
         n = vss.num_fields
@@ -585,7 +683,7 @@ class Actuated(_ChannelWrapper):
         policy = isinstance(team, (SnapshotOpponent, OpponentPool))
         if actuated is None:
             actuated = policy
-        perceived = {"perceived": policy} if isinstance(self.env, (Perceived, Estimated)) else {}  # its isinstance sees the team
+        perceived = {"perceived": policy} if isinstance(self.env, (Perceived, Tracked, Estimated)) else {}  # its isinstance sees the team
         if team is None or not actuated:
             self.env.set_opponent(team, **perceived)
             self.opponent_channel = None

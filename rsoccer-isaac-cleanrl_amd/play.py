@@ -133,14 +133,15 @@ def baseline_teams(root="base_nets", device="cuda:0"):
 
 @torch.no_grad()
 def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk=32, perceive=None, actuate=None,
-                 estimate=None):
+                 estimate=None, track=None):
     """Mean blue goal score and episode length over the first `n_matches` finished episodes.  `perceive`: a
     vss_amd.perceive.PerceptionChannel over the blue rows of the FULL layout (layout_full_blue, rows = 6 N);
     blue then acts on what the camera would have delivered, yellow on the truth.  `actuate`: a
     vss_amd.actuate.ActuationChannel over the blue half of the FULL action buffer (layout_full_blue, rows = 6 N);
     blue's commands then pass it in place, started afresh here, and yellow's stay exact.  `estimate`: a
     vss_amd.estimate.EstimationChannel over the same blue rows, applied after `perceive`: blue acts on the perceived
-    rows rolled forward to the present."""
+    rows rolled forward to the present.  `track`: a vss_amd.track.TrackingChannel over the same blue rows, applied
+    after `perceive` and before `estimate`: the perceived rows filtered across frames."""
     envs.reset_buf[:] = 1
     envs.reset_dones()  # like the reference, obs_buf is not recomputed here (play.py:132-151)
     n = envs.num_fields
@@ -148,6 +149,8 @@ def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk
     action_buf = torch.zeros((n,) + tuple(envs.action_space.shape), device=envs.device)
     obs = envs.reset()["obs"]
     blue_obs = obs if perceive is None else perceive.start(obs)
+    if track is not None:
+        blue_obs = track.start(blue_obs)
     if estimate is not None:
         blue_obs = estimate.start(blue_obs)
     dones = None
@@ -173,6 +176,8 @@ def play_matches(envs, blue_team, yellow_team, n_matches, video_path=None, chunk
             obs = o["obs"]
             # (no terminal row is used here: the true rows stand in for it)
             blue_obs = obs if perceive is None else perceive.perceive(obs, obs, dones)[0]
+            if track is not None:
+                blue_obs = track.track(blue_obs, blue_obs, dones)[0]
             if estimate is not None:
                 blue_obs = estimate.estimate(blue_obs, blue_obs, dones)[0]
             d = dones[:k] != 0

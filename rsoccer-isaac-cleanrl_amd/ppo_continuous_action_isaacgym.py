@@ -29,8 +29,8 @@ the loop -- and the machinery under it lives in vss_amd/:
   learner rows, two per field (dma: six);
 * `--opponent scripted` (a build addition): the yellow team is the scripted benchmark team (vss_amd/scripted.py,
   one vss_scripted_team launch per step) -- a fixed opponent that plays, with nothing to snapshot or sync;
-* `--obs-delay D --obs-noise-*`, `--obs-predict 1`, `--act-*` (build additions): rows D steps late with pose noise
-  (perceive.py), rolled forward to the present (estimate.py), commands through imperfect motors (actuate.py); 0: off;
+* `--obs-delay D --obs-noise-*`, `--obs-filter-*`, `--obs-predict 1`, `--act-*` (build additions): rows D steps late with
+  pose noise (perceive.py), filtered (track.py), rolled forward (estimate.py), imperfect motors (actuate.py); 0: off;
 * `--eval-every K` (a build addition): every K-th update rank 0 plays the live agent against fixed teams on a
   separate arena env (vss_amd/arena.py) and adds the scores to the update's record; the training's bits do not move.
 """
@@ -155,7 +155,7 @@ def parse_args(argv=None):
         p.add_argument(f"--obs-noise-{k}", type=float, default=0.0, help=f"vision noise: std of every {what}; 0: none")
     p.add_argument("--checkpoint-every", type=int, default=0, help="every K-th update: <run>-state.pt, <run>-agent-u<update>.pt")
     p.add_argument("--resume", type=str, default=None, help="a <run>-state.pt: go on after its update, bit-equal (DESIGN.md §15)")
-    args = CK.check_estimation(CK.add_channel_arguments(p).parse_args(argv))  # + --act-* (Actuated), --obs-predict (Estimated)
+    args = CK.check_tracking(CK.check_estimation(CK.add_channel_arguments(p).parse_args(argv)))  # + --act-*, --obs-predict / -filter-*
     args.batch_size = int(args.num_envs * args.num_steps)
     args.minibatch_size = int(args.batch_size // args.num_minibatches)
     return args

@@ -56,14 +56,15 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "vss.h"
 REBUILD = "`make -C {csrc}` or `python -c 'import __graft_entry__ as g; g.build()'`"
 
 
-def _stamped() -> tuple:
+def _stamped(csrc: str | None = None) -> tuple:
     """The files csrc/Makefile stamps into libvss_amd.so, in its order: the words of its STAMPED line, each without
-    the ":<flag set>" a translation unit carries there."""
-    with open(os.path.join(CSRC, "Makefile")) as f:
+    the ":<flag set>" a translation unit carries there.  (`csrc`: another unit's directory, e.g. csrc_track.)"""
+    csrc = CSRC if csrc is None else csrc
+    with open(os.path.join(csrc, "Makefile")) as f:
         line = re.search(r"^STAMPED\s*:?=\s*(\S.*)$", f.read(), re.M)
     if not line:
-        raise NativeError(f"{CSRC}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
-    return tuple(os.path.normpath(os.path.join(CSRC, word.split(":")[0])) for word in line.group(1).split())
+        raise NativeError(f"{csrc}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
+    return tuple(os.path.normpath(os.path.join(csrc, word.split(":")[0])) for word in line.group(1).split())
 
 
 STAMPED = _stamped()
@@ -78,10 +79,10 @@ globals().update({"".join("IO" if part == "io" else part.capitalize() for part i
 _lib = None
 
 
-def source_hash() -> str:
-    """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
+def source_hash(stamped: tuple | None = None) -> str:
+    """sha256 (first 16 hex digits) of the stamped sources as they are in this tree (`stamped`: another unit's)."""
     h = hashlib.sha256()
-    for path in STAMPED:
+    for path in STAMPED if stamped is None else stamped:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

@@ -68,6 +68,10 @@ class Arena:
             delay, noise = perception_args(args)
             if delay or noise.any():
                 self.wrapper = Perceived(self.wrapper, delay, noise, perception_seed(args.seed, 1))
+            # --obs-filter-*: the perceived rows filtered across frames, as in training; reset() starts the channel afresh
+            from envs.wrappers import Tracked, tracking_args
+            if tracking_args(args).any():
+                self.wrapper = Tracked(self.wrapper, tracking_args(args))
             # --obs-predict 1: the perceived rows rolled forward, as in training; reset() starts the channel afresh
             from envs.wrappers import Estimated, estimation_args
             if estimation_args(args):

@@ -1,5 +1,5 @@
-"""What the perception, the actuation and the estimation channel (perceive.py, actuate.py, estimate.py) share on the
-kernel's side: where a layout's units lie, the checks on the buffers a call is handed, and the checkpoint entries.
+"""What the perception, the actuation, the estimation and the tracking channel (perceive.py, actuate.py, estimate.py,
+track.py) share on the kernel's side: where a layout's units lie, the checks on the buffers a call is handed, and the checkpoint entries.
 
 A layout is a NamedTuple that begins (field_stride, team_stride, robots, n_teams); a unit is what its strides count:
 a 52-float observation row, or a robot's two command floats."""
@@ -25,7 +25,7 @@ def index(layout, n_fields: int) -> np.ndarray:
 
 
 class Channel:
-    """The base of the three channel classes.  A subclass sets device, n_fields, layout and done_stride, calls
+    """The base of the four channel classes.  A subclass sets device, n_fields, layout and done_stride, calls
     _set_rows(), and names its device tensors in _state_tensors(); the checkpoint label is the class's name."""
     unit = "rows"            # what the layout counts, for the messages
     width = 52               # floats per unit

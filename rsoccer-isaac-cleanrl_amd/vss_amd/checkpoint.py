@@ -32,6 +32,10 @@ PERCEPTION_STRUCTURAL = ("obs_delay", "obs_noise_pos", "obs_noise_vel", "obs_noi
 ACTUATION_STRUCTURAL = ("act_gain", "act_noise", "act_levels", "act_deadband", "act_loss")
 # the estimation channel's flag (vss_amd/estimate.py): structural in the same way, 0 where a state file lacks it
 ESTIMATION_STRUCTURAL = ("obs_predict",)
+# the tracking channel's flags (vss_amd/track.py): structural in the same way; a state file that lacks one has its default
+TRACKING_STRUCTURAL = ("obs_filter_team", "obs_filter_opp", "obs_filter_ball", "obs_filter_gate_pos", "obs_filter_gate_vel")
+TRACKING_DEFAULTS = dict(obs_filter_team=0.0, obs_filter_opp=0.0, obs_filter_ball=0.0, obs_filter_gate_pos=0.03,
+                         obs_filter_gate_vel=0.5)
 # set by train() itself or about the checkpoint, not hyper-parameters: never reported as changed
 _NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
 
@@ -55,9 +59,41 @@ def add_estimation_arguments(p):
     return p
 
 
+def add_tracking_arguments(p):
+    """The command line's tracking flags: the keys of TRACKING_STRUCTURAL with TRACKING_DEFAULTS (envs/wrappers.py
+    Tracked).  Returns the parser."""
+    d = TRACKING_DEFAULTS
+    p.add_argument("--obs-filter-team", type=float, default=d["obs_filter_team"],
+                   help="tracking: the filter's gain on the own robots, in [0, 1]; 0: not filtered (Tracked)")
+    p.add_argument("--obs-filter-opp", type=float, default=d["obs_filter_opp"], help="tracking: the gain on the opponents")
+    p.add_argument("--obs-filter-ball", type=float, default=d["obs_filter_ball"], help="tracking: the gain on the ball")
+    p.add_argument("--obs-filter-gate-pos", type=float, default=d["obs_filter_gate_pos"],
+                   help="tracking: a body further than this (m, x or y) from its prediction is re-initialised; 0: off")
+    p.add_argument("--obs-filter-gate-vel", type=float, default=d["obs_filter_gate_vel"],
+                   help="tracking: the same for the velocity (m/s); 0: off")
+    return p
+
+
 def add_channel_arguments(p):
-    """The actuation and the estimation flags.  Returns the parser."""
-    return add_estimation_arguments(add_actuation_arguments(p))
+    """The actuation, the estimation and the tracking flags.  Returns the parser."""
+    return add_tracking_arguments(add_estimation_arguments(add_actuation_arguments(p)))
+
+
+def check_tracking(args):
+    """Refuse tracking gains outside [0, 1], negative or non-finite gates, and a gain without vision noise: the filter
+    averages noise across frames, and with every --obs-noise-* at 0 there is nothing to filter.  Returns args."""
+    get = lambda k: float(TRACKING_DEFAULTS[k] if getattr(args, k, None) is None else getattr(args, k))  # noqa: E731
+    gains = [get(k) for k in TRACKING_STRUCTURAL[:3]]
+    for k, g in zip(TRACKING_STRUCTURAL[:3], gains):
+        if not 0.0 <= g <= 1.0:
+            raise ValueError(f"--{k.replace('_', '-')} must be in [0, 1], got {g}")
+    for k in TRACKING_STRUCTURAL[3:]:
+        if not 0.0 <= get(k) < float("inf"):
+            raise ValueError(f"--{k.replace('_', '-')} must be finite and >= 0, got {get(k)}")
+    if any(gains) and not any(float(getattr(args, f"obs_noise_{k}", 0.0) or 0.0) for k in ("pos", "vel", "ang", "angvel")):
+        raise ValueError("--obs-filter-* needs vision noise (--obs-noise-pos / -vel / -ang / -angvel): the tracker "
+                         "filters noise across frames, and without noise there is nothing to filter")
+    return args
 
 
 def check_estimation(args):
@@ -88,12 +124,14 @@ def check_compatible(saved_args, args, log=print) -> list:
     ValueError naming the key and both values; every other argument is taken from `args`, and each one that
     differs from the saved value is reported once through `log` (None: silent).  Returns the changed keys."""
     saved, new = plain_args(saved_args), plain_args(args)
-    for k in STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL:
+    for k in STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL + TRACKING_STRUCTURAL:
         a, b = saved.get(k), new.get(k)
         if k == "opponent":
             a, b = opponent_mode(a), opponent_mode(b)
         if k in PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL:
             a, b = a or 0, b or 0
+        if k in TRACKING_STRUCTURAL:
+            a, b = (TRACKING_DEFAULTS[k] if v is None else v for v in (a, b))
         if a != b:
             raise ValueError(f"--resume: {k} is structural and differs: the state file has {a!r}, this command line {b!r}")
     changed = []
