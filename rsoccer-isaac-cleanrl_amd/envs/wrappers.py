@@ -72,6 +72,10 @@ def make_env(args):
         raise ValueError(f"--opponent must be ou, self, pool, mirror, scripted or a checkpoint path, got {opponent!r}")
     # the opponent itself (a snapshot of the Agent) is set by the train loop: set_opponent()
     wrapped = wrappers[args.env_id](envs)
+    table = setplay_table(args)
+    if table is not None:  # --setplay-share > 0: inside every channel wrapper; with 0 the chain is as without the flags
+        from vss_amd.setplay import Stager
+        wrapped.set_setplays(Stager(envs.num_fields, table, setplay_seed(getattr(args, "seed", None)), envs.device))
     delay, noise = perception_args(args)
     if delay or noise.any():  # --obs-delay / --obs-noise-*: with all of them zero the chain is as without the flags
         wrapped = Perceived(wrapped, delay, noise, perception_seed(getattr(args, "seed", None)))
@@ -84,6 +88,20 @@ def make_env(args):
     if params.any():  # --act-*: the outermost wrapper; with all of them zero the chain is as without the flags
         wrapped = Actuated(wrapped, params, actuation_seed(getattr(args, "seed", None)))
     return envs, wrapped
+
+
+def setplay_table(args):
+    """The set-play table of --setplay-share / --setplay-mix / --setplay-file (vss_amd/setplay.py); None with a share
+    of 0, the default."""
+    from vss_amd.setplay import table_of_args
+    return table_of_args(args)
+
+
+def setplay_seed(seed, offset: int = 0) -> int:
+    """The stager's Philox key, built as perception_seed with a constant of its own; `offset` separates the arena's
+    stager (1) from the training's."""
+    from vss_amd.setplay import setplay_seed as key
+    return key(seed, offset)
 
 
 def perception_args(args):
@@ -263,6 +281,7 @@ class _FusedWrapper(Wrapper):
         env.compute_observations(self._obs, n_agents=3 if self.ROWS_PER_FIELD == 3 else 1)
         self._opponent = None  # yellow team policy (set_opponent); None: the kernel's OU process
         self._opp_obs = self._opp_act = None
+        self._setplays = None  # vss_amd.setplay.Stager (set_setplays); None: every episode starts from the uniform drop
 
     def _first_obs(self):
         self.env.compute_observations(self._obs, n_agents=3 if self.ROWS_PER_FIELD == 3 else 1)
@@ -275,6 +294,22 @@ class _FusedWrapper(Wrapper):
         full = torch.empty((env.num_fields, 2, 3, env.num_obs), device=env.device)
         env.compute_observations(full, n_agents=6)
         self._opp_obs.copy_(full[:, 1])
+
+    def _setplay_views(self):
+        """The rows a staged field rewrites: the learner's and, with a policy opponent, the versus step's opp_obs."""
+        from vss_amd import setplay as S
+        views = [(self._obs, S.view_dma() if self.ROWS_PER_FIELD == 3 else S.view_sa())]
+        if self._opponent is not None:
+            views.append((self._opp_obs, S.view_opponent()))
+        return views
+
+    def set_setplays(self, stager=None):
+        """Start a share of the episodes from the stager's set plays (vss_amd/setplay.py): one start
+        call here, on the fresh fields, so the first episodes follow the mix as well, then one vss_setplay launch
+        after every step.  None (the default) restores the uniform drop alone and step() is as before."""
+        self._setplays = stager
+        if stager is not None:
+            stager.start(self.env.state, self._setplay_views())
 
     def set_opponent(self, team=None):
         """Drive the yellow team with `team` -- play.py's protocol, team(act (N,3,2) written in place,
@@ -307,10 +342,15 @@ class _FusedWrapper(Wrapper):
         """The wrapper's own buffers on the CPU (vss_amd.checkpoint): the OU state, the learner's current
         observations (the next rollout's first input) and the other outputs, the opponent's rows when one is
         set.  The env's and the opponent's state are saved by their owners."""
-        return to_cpu({k: t for k, t in self._state_tensors().items() if t is not None})
+        out = to_cpu({k: t for k, t in self._state_tensors().items() if t is not None})
+        if self._setplays is not None:
+            out["setplays"] = self._setplays.state_dict()
+        return out
 
     def load_state_dict(self, state: dict) -> None:
         copy_entries(type(self).__name__, self._state_tensors(), state)
+        if self._setplays is not None:
+            self._setplays.load_state_dict(entry(state, "setplays", type(self).__name__))
 
     def _rews_view(self):
         return self._rews
@@ -331,6 +371,8 @@ class _FusedWrapper(Wrapper):
             if hasattr(self._opponent, "observe"):  # a league counts the finished fields' results per slot
                 self._opponent.observe(self._rews, env.reset_buf if self._dones is None else self._dones,
                                        self._progress)
+        if self._setplays is not None:  # the fields the step has just reset: a share of them from a set play
+            self._setplays.stage(env.state, self._setplay_views(), env.reset_buf)
         dones = env.reset_buf if self._dones is None else self._dones
         return {"obs": self._obs}, self._reward, dones, infos
 
@@ -742,7 +784,18 @@ class _MirrorWrapper(Wrapper):
         self._yl = dict(obs=yellow(self._obs), terminal_obs=yellow(self._terminal_obs), rew=yellow(self._rews),
                         reward_sum=yellow(self._reward), dones=yellow(self._dones), time_outs=yellow(self._time_outs),
                         progress_f=yellow(self._progress))
+        self._setplays = None  # vss_amd.setplay.Stager (set_setplays)
         self._first_obs()
+
+    def _setplay_views(self):
+        from vss_amd import setplay as S
+        return [(self._obs, S.view_mirror(self.FIELD_ROWS, self.env.num_fields))]
+
+    def set_setplays(self, stager=None):
+        """As _FusedWrapper.set_setplays: both team blocks are one two-team view."""
+        self._setplays = stager
+        if stager is not None:
+            stager.start(self.env.state, self._setplay_views())
 
     def _first_obs(self):
         env, R = self.env, self.FIELD_ROWS
@@ -760,10 +813,15 @@ class _MirrorWrapper(Wrapper):
 
     def state_dict(self) -> dict:
         """The full-row tensors on the CPU (vss_amd.checkpoint); the `_io` / `_yl` halves are views of them."""
-        return to_cpu(self._state_tensors())
+        out = to_cpu(self._state_tensors())
+        if self._setplays is not None:
+            out["setplays"] = self._setplays.state_dict()
+        return out
 
     def load_state_dict(self, state: dict) -> None:
         copy_entries(type(self).__name__, self._state_tensors(), state)
+        if self._setplays is not None:
+            self._setplays.load_state_dict(entry(state, "setplays", type(self).__name__))
 
     def reset(self, **kwargs):
         self.env.reset(**kwargs)
@@ -771,6 +829,8 @@ class _MirrorWrapper(Wrapper):
 
     def step(self, action):
         self.env.native_step_mirror(self.MODE, action, self._io, self._yl)
+        if self._setplays is not None:
+            self._setplays.stage(self.env.state, self._setplay_views(), self.env.reset_buf)
         infos = {"rews": self._rews, "terminal_observation": self._terminal_obs, "time_outs": self._time_outs,
                  "progress_buffer": self._progress}
         return {"obs": self._obs}, self._reward, self._dones, infos

@@ -16,6 +16,11 @@ An evaluation is a pure function of (weights, --seed, update): before each team'
 zeroed and the policy's Philox counter is set from the update number.  So the arena owns no state a checkpoint
 must carry -- a resumed run reports the evaluations of the unbroken one -- and it touches nothing of the
 training: not its env, not its policy's counter, not torch's generators (forked around the run).
+
+`--eval-setplays a,b` (vss_amd/setplay.py): for each team and each named play every field's first episode also starts
+from that play -- after reset_dones() a stager of the arena's own (a key of its own, its call index set from the update
+number) stages every field with it (`only=`) -- and is recorded as "<team>@<play>".  Later episodes of a field start
+from the uniform drop and are not counted.
 """
 from __future__ import annotations
 
@@ -34,6 +39,14 @@ def parse_teams(spec) -> list:
     bad = [t for t in names if t not in TEAMS]
     if bad or not names or len(set(names)) != len(names):
         raise ValueError(f"--eval-teams takes distinct names out of {', '.join(TEAMS)}, comma separated; got {spec!r}")
+    return names
+
+
+def parse_setplays(spec) -> list:
+    """--eval-setplays as a list of distinct play names (vss_amd/setplay.py named_play checks them); empty: none."""
+    names = [t.strip() for t in str(spec or "").split(",") if t.strip()]
+    if len(set(names)) != len(names):
+        raise ValueError(f"--eval-setplays takes distinct play names, comma separated; got {spec!r}")
     return names
 
 
@@ -83,6 +96,12 @@ class Arena:
                 self.wrapper = Actuated(self.wrapper, params, actuation_seed(args.seed, 1))
             self.policy = FusedPolicy(agent, seed=int(args.seed) * 7919 + 15485863, actor_only=True)
         self.opponents = {t: (None if t == "ou" else get_team(t)) for t in self.teams}
+        self.setplays, self.stager = parse_setplays(getattr(args, "eval_setplays", "")), None
+        if self.setplays:
+            from . import setplay as S
+            library = dict(S.BUILTIN, **(S.load_file(args.setplay_file) if getattr(args, "setplay_file", None) else {}))
+            table = S.Table([S.named_play(name, library) for name in self.setplays], 1.0)
+            self.stager = S.Stager(n, table, S.setplay_seed(args.seed, 1), self.device)
         self.n_fields = n
         self.rows_per_field = self.wrapper.ROWS_PER_FIELD
         rows = n * self.rows_per_field
@@ -92,13 +111,18 @@ class Arena:
         self.steps = int(env.max_episode_length)
 
     @torch.no_grad()
-    def play(self, team: str, counter: int) -> dict:
-        """Every field's first episode against `team`, the policy's Philox counter starting above `counter`."""
+    def play(self, team: str, counter: int, setplay: int | None = None) -> dict:
+        """Every field's first episode against `team`, the policy's Philox counter starting above `counter`;
+        `setplay`: the index in --eval-setplays of the play every field starts from (None: the uniform drop)."""
         env, w, lib = self.env, self.wrapper, N.load()
         env.rng_counter.zero_()
         env.reset_buf.fill_(1)
         env.reset_dones()
         w.action_buf.zero_()
+        if setplay is not None:  # the state alone: reset() below derives every row from it
+            self.stager.call = int(counter) & 0xFFFFFFFF
+            self.stager.counts.zero_()
+            self.stager.start(env.state, (), only=int(setplay))
         w.set_opponent(self.opponents[team])
         obs = w.reset()["obs"]
         self.policy.counter = int(counter)
@@ -121,7 +145,12 @@ class Arena:
         """{team: {score, wins, losses, draws, length}} of the agent's current weights at `update`."""
         with torch.random.fork_rng(devices=[self.device]):
             self.policy.refresh()
-            return {t: self.play(t, (int(update) * len(self.teams) + i) * self.steps) for i, t in enumerate(self.teams)}
+            out = {t: self.play(t, (int(update) * len(self.teams) + i) * self.steps) for i, t in enumerate(self.teams)}
+            for i, t in enumerate(self.teams):  # counters of their own, above every plain evaluation's
+                for j, name in enumerate(self.setplays):
+                    at = (int(update) * len(self.teams) + i) * len(self.setplays) + j
+                    out[f"{t}@{name}"] = self.play(t, (1 << 40) + at * self.steps, setplay=j)
+            return out
 
     def evaluate_into(self, rec: dict, update: int, writer, start_time: float) -> None:
         """The train loop's call: rec["eval"], rec["eval_s"], the writer's eval/* scalars; rec["wall_s"] and

@@ -7,9 +7,11 @@
     bind(lib, h)                          # set them on a ctypes.CDLL
 
 Pointers (members, parameters, array parameters) are c_void_p: callers pass data_ptr() ints, None, byref(struct)
-and ctypes arrays.  Scalars map through SCALARS.  Anything else -- a type outside the table, a struct by value, a
-bit-field, a union, a nested struct, a statement that is neither a struct nor a prototype -- raises HeaderError
-with the name and the token: a guessed type would truncate a pointer silently, so there is no guess.
+and ctypes arrays.  Scalars map through SCALARS.  A struct member may also be a struct that the header defined
+earlier, by value or as an array (vss_setplay_play's entities).  Anything else -- a type outside the table, a struct
+by value as a parameter or a result, a bit-field, a union, a struct defined inside a struct, a statement that is
+neither a struct nor a prototype -- raises HeaderError with the name and the token: a guessed type would truncate a
+pointer silently, so there is no guess.
 stdlib only (no torch): tools and tests can parse a header without loading the GPU runtime.
 """
 from __future__ import annotations
@@ -42,7 +44,7 @@ def _ctype(decl: str, where: str):
     return SCALARS[words[0]]
 
 
-def _struct(name: str, body: str, constants: dict) -> type:
+def _struct(name: str, body: str, constants: dict, structs: dict | None = None) -> type:
     bad = re.search(r"[{:]|\b(struct|union|enum)\b", body)
     if bad:
         raise HeaderError(f"struct {name}: '{bad.group()}' (nested struct, union, enum or bit-field) is not supported")
@@ -53,7 +55,11 @@ def _struct(name: str, body: str, constants: dict) -> type:
         if not m or not m.group(1).strip():
             raise HeaderError(f"struct {name}: cannot parse member '{decl}'")
         base, member, length = m.groups()
-        ctype = _ctype(base, f"struct {name}.{member}")
+        words = [w for w in base.split() if w != "const"]
+        if structs and len(words) == 1 and words[0] in structs:  # a struct the header defined earlier, by value
+            ctype = structs[words[0]]
+        else:
+            ctype = _ctype(base, f"struct {name}.{member}")
         if length is not None:
             if not (length.isdigit() or length in constants):
                 raise HeaderError(f"struct {name}.{member}: array length '{length}' is not an integer or a #define")
@@ -102,7 +108,7 @@ def parse(text: str) -> Header:
             raise HeaderError(f"struct {name}: typedef'd under another name, '{alias}'")
         if name in structs:
             raise HeaderError(f"struct {name}: defined twice")
-        structs[name] = _struct(name, body, constants)
+        structs[name] = _struct(name, body, constants, structs)
         return " "
     text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{((?:[^{}]|\{[^{}]*\})*)\}\s*(\w+)\s*;", take_struct, text)
 

@@ -36,6 +36,10 @@ ESTIMATION_STRUCTURAL = ("obs_predict",)
 TRACKING_STRUCTURAL = ("obs_filter_team", "obs_filter_opp", "obs_filter_ball", "obs_filter_gate_pos", "obs_filter_gate_vel")
 TRACKING_DEFAULTS = dict(obs_filter_team=0.0, obs_filter_opp=0.0, obs_filter_ball=0.0, obs_filter_gate_pos=0.03,
                          obs_filter_gate_vel=0.5)
+# the set plays' flags (vss_amd/setplay.py): structural in the same way -- the stager is a state owner and its table
+# decides every staged episode; a state file that lacks one has its default
+SETPLAY_STRUCTURAL = ("setplay_share", "setplay_mix", "setplay_file")
+SETPLAY_DEFAULTS = dict(setplay_share=0.0, setplay_mix=None, setplay_file=None)
 # set by train() itself or about the checkpoint, not hyper-parameters: never reported as changed
 _NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
 
@@ -74,9 +78,22 @@ def add_tracking_arguments(p):
     return p
 
 
+def add_setplay_arguments(p):
+    """The command line's set-play flags: the keys of SETPLAY_STRUCTURAL (envs/wrappers.py set_setplays) and the
+    arena's --eval-setplays.  Returns the parser."""
+    p.add_argument("--setplay-share", type=float, default=0.0,
+                   help="set plays: the share of episodes that start from a named placement (0: none, the default)")
+    p.add_argument("--setplay-mix", type=str, default=None,
+                   help="set plays: name:weight,... e.g. kickoff:1,free_ball:2,penalty_for:1 (default: every built-in at 1)")
+    p.add_argument("--setplay-file", type=str, default=None, help="set plays: a JSON file of custom plays (settings only)")
+    p.add_argument("--eval-setplays", type=str, default="",
+                   help="arena: also score the agent from each of these set plays, e.g. penalty_for,penalty_against")
+    return p
+
+
 def add_channel_arguments(p):
-    """The actuation, the estimation and the tracking flags.  Returns the parser."""
-    return add_tracking_arguments(add_estimation_arguments(add_actuation_arguments(p)))
+    """The actuation, the estimation, the tracking and the set-play flags.  Returns the parser."""
+    return add_setplay_arguments(add_tracking_arguments(add_estimation_arguments(add_actuation_arguments(p))))
 
 
 def check_tracking(args):
@@ -124,7 +141,8 @@ def check_compatible(saved_args, args, log=print) -> list:
     ValueError naming the key and both values; every other argument is taken from `args`, and each one that
     differs from the saved value is reported once through `log` (None: silent).  Returns the changed keys."""
     saved, new = plain_args(saved_args), plain_args(args)
-    for k in STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL + TRACKING_STRUCTURAL:
+    for k in (STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL + TRACKING_STRUCTURAL
+              + SETPLAY_STRUCTURAL):
         a, b = saved.get(k), new.get(k)
         if k == "opponent":
             a, b = opponent_mode(a), opponent_mode(b)
@@ -132,6 +150,10 @@ def check_compatible(saved_args, args, log=print) -> list:
             a, b = a or 0, b or 0
         if k in TRACKING_STRUCTURAL:
             a, b = (TRACKING_DEFAULTS[k] if v is None else v for v in (a, b))
+        if k == "setplay_share":
+            a, b = float(a or 0.0), float(b or 0.0)
+        if k in SETPLAY_STRUCTURAL[1:]:
+            a, b = a or None, b or None
         if a != b:
             raise ValueError(f"--resume: {k} is structural and differs: the state file has {a!r}, this command line {b!r}")
     changed = []
