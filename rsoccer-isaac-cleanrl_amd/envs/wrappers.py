@@ -76,6 +76,10 @@ def make_env(args):
     if table is not None:  # --setplay-share > 0: inside every channel wrapper; with 0 the chain is as without the flags
         from vss_amd.setplay import Stager
         wrapped.set_setplays(Stager(envs.num_fields, table, setplay_seed(getattr(args, "seed", None)), envs.device))
+    from vss_amd.referee import referee_of_args
+    referee = referee_of_args(args, envs.num_fields, envs.device)
+    if referee is not None:  # --ref-stall-steps / --ref-area-steps > 0: beside the stager; else the chain is as before
+        wrapped.set_referee(referee)
     delay, noise = perception_args(args)
     if delay or noise.any():  # --obs-delay / --obs-noise-*: with all of them zero the chain is as without the flags
         wrapped = Perceived(wrapped, delay, noise, perception_seed(getattr(args, "seed", None)))
@@ -255,6 +259,16 @@ class RecordEpisodeStatisticsTorch(Wrapper):
         return observations, rewards, dones, infos
 
 
+def _referee_record(ref, rec: dict, writer=None, step: int = 0) -> None:
+    """The train loop's call on a fused or mirror wrapper, once per update: the referee's calls since the last one go
+    into `rec` and to the writer as referee/free_ball, /penalty_for, /penalty_against, /goal_kick_for,
+    /goal_kick_against ("for": blue's to take) -- one host read of eight counts; nothing without a referee."""
+    for k, v in (ref.record() if ref is not None else {}).items():
+        rec[k] = v
+        if writer is not None:
+            writer.add_scalar(k, v, step)
+
+
 class _FusedWrapper(Wrapper):
     """Common part of SA / CMA / DMA: the OU action buffer and the packed output buffers."""
 
@@ -282,6 +296,7 @@ class _FusedWrapper(Wrapper):
         self._opponent = None  # yellow team policy (set_opponent); None: the kernel's OU process
         self._opp_obs = self._opp_act = None
         self._setplays = None  # vss_amd.setplay.Stager (set_setplays); None: every episode starts from the uniform drop
+        self._referee = None  # vss_amd.referee.Referee (set_referee); None: nothing is whistled inside an episode
 
     def _first_obs(self):
         self.env.compute_observations(self._obs, n_agents=3 if self.ROWS_PER_FIELD == 3 else 1)
@@ -310,6 +325,15 @@ class _FusedWrapper(Wrapper):
         self._setplays = stager
         if stager is not None:
             stager.start(self.env.state, self._setplay_views())
+
+    def set_referee(self, ref=None):
+        """Call free balls, penalties and goal kicks inside the episodes (vss_amd/referee.py): one
+        vss_referee launch after every step, after the set plays, over the set plays' views.  None (the default):
+        step() is as before."""
+        self._referee = ref
+
+    def referee_record(self, rec: dict, writer=None, step: int = 0) -> None:
+        _referee_record(self._referee, rec, writer, step)
 
     def set_opponent(self, team=None):
         """Drive the yellow team with `team` -- play.py's protocol, team(act (N,3,2) written in place,
@@ -345,12 +369,16 @@ class _FusedWrapper(Wrapper):
         out = to_cpu({k: t for k, t in self._state_tensors().items() if t is not None})
         if self._setplays is not None:
             out["setplays"] = self._setplays.state_dict()
+        if self._referee is not None:
+            out["referee"] = self._referee.state_dict()
         return out
 
     def load_state_dict(self, state: dict) -> None:
         copy_entries(type(self).__name__, self._state_tensors(), state)
         if self._setplays is not None:
             self._setplays.load_state_dict(entry(state, "setplays", type(self).__name__))
+        if self._referee is not None:
+            self._referee.load_state_dict(entry(state, "referee", type(self).__name__))
 
     def _rews_view(self):
         return self._rews
@@ -373,6 +401,9 @@ class _FusedWrapper(Wrapper):
                                        self._progress)
         if self._setplays is not None:  # the fields the step has just reset: a share of them from a set play
             self._setplays.stage(env.state, self._setplay_views(), env.reset_buf)
+        if self._referee is not None:  # the fields that go on: stoppages; the fields just reset: their counters zeroed
+            self._referee.call(env.state, env.dof_velocity_buf, self._setplay_views(), env.reset_buf)
+            infos["referee"] = self._referee.verdict
         dones = env.reset_buf if self._dones is None else self._dones
         return {"obs": self._obs}, self._reward, dones, infos
 
@@ -785,6 +816,7 @@ class _MirrorWrapper(Wrapper):
                         reward_sum=yellow(self._reward), dones=yellow(self._dones), time_outs=yellow(self._time_outs),
                         progress_f=yellow(self._progress))
         self._setplays = None  # vss_amd.setplay.Stager (set_setplays)
+        self._referee = None  # vss_amd.referee.Referee (set_referee)
         self._first_obs()
 
     def _setplay_views(self):
@@ -796,6 +828,13 @@ class _MirrorWrapper(Wrapper):
         self._setplays = stager
         if stager is not None:
             stager.start(self.env.state, self._setplay_views())
+
+    def set_referee(self, ref=None):
+        """As _FusedWrapper.set_referee: both team blocks are one two-team view."""
+        self._referee = ref
+
+    def referee_record(self, rec: dict, writer=None, step: int = 0) -> None:
+        _referee_record(self._referee, rec, writer, step)
 
     def _first_obs(self):
         env, R = self.env, self.FIELD_ROWS
@@ -816,12 +855,16 @@ class _MirrorWrapper(Wrapper):
         out = to_cpu(self._state_tensors())
         if self._setplays is not None:
             out["setplays"] = self._setplays.state_dict()
+        if self._referee is not None:
+            out["referee"] = self._referee.state_dict()
         return out
 
     def load_state_dict(self, state: dict) -> None:
         copy_entries(type(self).__name__, self._state_tensors(), state)
         if self._setplays is not None:
             self._setplays.load_state_dict(entry(state, "setplays", type(self).__name__))
+        if self._referee is not None:
+            self._referee.load_state_dict(entry(state, "referee", type(self).__name__))
 
     def reset(self, **kwargs):
         self.env.reset(**kwargs)
@@ -833,6 +876,9 @@ class _MirrorWrapper(Wrapper):
             self._setplays.stage(self.env.state, self._setplay_views(), self.env.reset_buf)
         infos = {"rews": self._rews, "terminal_observation": self._terminal_obs, "time_outs": self._time_outs,
                  "progress_buffer": self._progress}
+        if self._referee is not None:
+            self._referee.call(self.env.state, self.env.dof_velocity_buf, self._setplay_views(), self.env.reset_buf)
+            infos["referee"] = self._referee.verdict
         return {"obs": self._obs}, self._reward, self._dones, infos
 
 

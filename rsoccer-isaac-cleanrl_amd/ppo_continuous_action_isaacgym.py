@@ -482,8 +482,7 @@ def train(args, on_update=None):
         t_roll = time.time()
         # per-env sums of finished episodes' returns and counts, reduced once after the rollout (two
         # elementwise launches per step instead of a product, two reductions and two adds)
-        ep_ret = torch.zeros(E, device=device)
-        ep_cnt = torch.zeros(E, device=device)
+        ep_ret, ep_cnt = torch.zeros(E, device=device), torch.zeros(E, device=device)
         # ppo…:273-279 logs the first finished env's episode stats at steps 0-2 (a host-sync loop);
         # here: [any done, goal, grad, move, energy, return, length] on the device, read once below
         ep_first = torch.zeros((3, 7), device=device)
@@ -553,6 +552,7 @@ def train(args, on_update=None):
         if opponent_mode == "mirror":  # rows are team-major: the halves of the per-row sums the loop keeps
             for team, half in (("blue", slice(0, E // 2)), ("yellow", slice(E // 2, E))):
                 rec[f"mean_return_{team}"] = float(ep_ret[half].sum() / ep_cnt[half].sum().clamp(min=1))
+        fused_env.referee_record(rec, writer, global_step)  # --ref-*: this update's stoppages (vss_amd/referee.py)
         history.append(rec)
         every = getattr(args, "opponent_update_every", 1)
         if opponent_mode == "pool":

@@ -21,6 +21,11 @@ training: not its env, not its policy's counter, not torch's generators (forked 
 from that play -- after reset_dones() a stager of the arena's own (a key of its own, its call index set from the update
 number) stages every field with it (`only=`) -- and is recorded as "<team>@<play>".  Later episodes of a field start
 from the uniform drop and are not counted.
+
+`--ref-*` (vss_amd/referee.py): when the training has a referee the arena's wrapper has one of its own with the same
+table and parameters (key offset 1, its counters zeroed and its call index set from the policy counter before every
+play), so an evaluation scores the game that is being trained and stays a pure function of (weights, seed, update);
+each result then carries "stoppages", the eight verdict counts of the play.
 """
 from __future__ import annotations
 
@@ -75,6 +80,10 @@ class Arena:
             env.w_goal, env.w_grad, env.w_move, env.w_energy = 1.0, 0.0, 0.0, 0.0  # as evaluate() sets them
             self.env = env
             self.wrapper = {"sa": SingleAgent, "cma": CMA, "dma": DMA}[args.env_id](env)
+            from .referee import referee_of_args
+            self.referee = referee_of_args(args, n, self.device, 1)  # None without --ref-*
+            if self.referee is not None:
+                self.wrapper.set_referee(self.referee)
             # --obs-delay / --obs-noise-*: blue sees perceived rows as in training, through a channel of the arena's
             # own (a key of its own); reset() starts it afresh at call 0 in every play, so it carries no state over
             from envs.wrappers import Perceived, perception_args, perception_seed
@@ -123,6 +132,8 @@ class Arena:
             self.stager.call = int(counter) & 0xFFFFFFFF
             self.stager.counts.zero_()
             self.stager.start(env.state, (), only=int(setplay))
+        if self.referee is not None:
+            self.referee.restart(counter)
         w.set_opponent(self.opponents[team])
         obs = w.reset()["obs"]
         self.policy.counter = int(counter)
@@ -138,8 +149,11 @@ class Arena:
                                         self.first.data_ptr(), info["progress_buffer"].data_ptr(), self.tally.data_ptr()),
                     "vss_match_tally")
         episodes, wins, losses, steps = self.tally[0].tolist()  # the one host read
-        return {"score": score(wins, losses, episodes), "wins": wins, "losses": losses, "draws": episodes - wins - losses,
-                "length": steps / episodes if episodes > 0 else 0.0}
+        out = {"score": score(wins, losses, episodes), "wins": wins, "losses": losses, "draws": episodes - wins - losses,
+               "length": steps / episodes if episodes > 0 else 0.0}
+        if self.referee is not None:
+            out["stoppages"] = self.referee.counts.tolist()
+        return out
 
     def evaluate(self, update: int) -> dict:
         """{team: {score, wins, losses, draws, length}} of the agent's current weights at `update`."""

@@ -27,7 +27,8 @@ def index(layout, n_fields: int) -> np.ndarray:
 class Channel:
     """The base of the four channel classes.  A subclass sets device, n_fields, layout and done_stride, calls
     _set_rows(), and names its device tensors in _state_tensors(); the checkpoint label is the class's name.
-    (setplay.Stager has no layout of its own -- its views come with every call -- and uses the checkpoint half.)"""
+    (setplay.Stager and referee.Referee have no layout of their own -- their views come with every call -- and use the
+    checkpoint half.)"""
     unit = "rows"            # what the layout counts, for the messages
     width = 52               # floats per unit
     scalars = {"call": int}  # the state_dict entries that are not tensors: attribute -> type

@@ -40,6 +40,11 @@ TRACKING_DEFAULTS = dict(obs_filter_team=0.0, obs_filter_opp=0.0, obs_filter_bal
 # decides every staged episode; a state file that lacks one has its default
 SETPLAY_STRUCTURAL = ("setplay_share", "setplay_mix", "setplay_file")
 SETPLAY_DEFAULTS = dict(setplay_share=0.0, setplay_mix=None, setplay_file=None)
+# the referee's flags (vss_amd/referee.py): structural in the same way -- the referee is a state owner and its
+# thresholds decide every stoppage; a state file that lacks one has its default
+REFEREE_STRUCTURAL = ("ref_stall_steps", "ref_stall_speed", "ref_area_steps", "ref_area_depth", "ref_area_width", "ref_max_stops")
+REFEREE_DEFAULTS = dict(ref_stall_steps=0, ref_stall_speed=0.05, ref_area_steps=0, ref_area_depth=0.15, ref_area_width=0.70,
+                        ref_max_stops=0)
 # set by train() itself or about the checkpoint, not hyper-parameters: never reported as changed
 _NOT_COMPARED = ("resume", "kernel_warmup_s", "graph_prepare_s")
 
@@ -91,9 +96,26 @@ def add_setplay_arguments(p):
     return p
 
 
+def add_referee_arguments(p):
+    """The command line's referee flags: the keys of REFEREE_STRUCTURAL with REFEREE_DEFAULTS (envs/wrappers.py
+    set_referee).  Returns the parser."""
+    d = REFEREE_DEFAULTS
+    p.add_argument("--ref-stall-steps", type=int, default=d["ref_stall_steps"],
+                   help="referee: a free ball after the ball has been slower than --ref-stall-speed for this many steps (0: off)")
+    p.add_argument("--ref-stall-speed", type=float, default=d["ref_stall_speed"], help="referee: the stuck ball's speed (m/s)")
+    p.add_argument("--ref-area-steps", type=int, default=d["ref_area_steps"],
+                   help="referee: a penalty (goal kick) after two defenders (attackers) have stood in a goal area with the "
+                        "ball for this many steps (0: off)")
+    p.add_argument("--ref-area-depth", type=float, default=d["ref_area_depth"], help="referee: the goal area's depth (m)")
+    p.add_argument("--ref-area-width", type=float, default=d["ref_area_width"], help="referee: the goal area's width (m)")
+    p.add_argument("--ref-max-stops", type=int, default=d["ref_max_stops"], help="referee: calls per episode (0: no cap)")
+    return p
+
+
 def add_channel_arguments(p):
-    """The actuation, the estimation, the tracking and the set-play flags.  Returns the parser."""
-    return add_setplay_arguments(add_tracking_arguments(add_estimation_arguments(add_actuation_arguments(p))))
+    """The actuation, the estimation, the tracking, the set-play and the referee flags.  Returns the parser."""
+    return add_referee_arguments(add_setplay_arguments(add_tracking_arguments(add_estimation_arguments(
+        add_actuation_arguments(p)))))
 
 
 def check_tracking(args):
@@ -142,7 +164,7 @@ def check_compatible(saved_args, args, log=print) -> list:
     differs from the saved value is reported once through `log` (None: silent).  Returns the changed keys."""
     saved, new = plain_args(saved_args), plain_args(args)
     for k in (STRUCTURAL + PERCEPTION_STRUCTURAL + ACTUATION_STRUCTURAL + ESTIMATION_STRUCTURAL + TRACKING_STRUCTURAL
-              + SETPLAY_STRUCTURAL):
+              + SETPLAY_STRUCTURAL + REFEREE_STRUCTURAL):
         a, b = saved.get(k), new.get(k)
         if k == "opponent":
             a, b = opponent_mode(a), opponent_mode(b)
@@ -154,6 +176,8 @@ def check_compatible(saved_args, args, log=print) -> list:
             a, b = float(a or 0.0), float(b or 0.0)
         if k in SETPLAY_STRUCTURAL[1:]:
             a, b = a or None, b or None
+        if k in REFEREE_STRUCTURAL:
+            a, b = (type(REFEREE_DEFAULTS[k])(REFEREE_DEFAULTS[k] if v is None else v) for v in (a, b))
         if a != b:
             raise ValueError(f"--resume: {k} is structural and differs: the state file has {a!r}, this command line {b!r}")
     changed = []
