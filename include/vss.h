@@ -862,6 +862,189 @@ int vss_estimate(void* stream, int64_t n_fields, const vss_estimate_layout* lay,
                  const float* obs, const float* term, const int64_t* done, int64_t done_stride, float* hist,
                  int32_t* age, float* obs_out, float* term_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * The tracking channel (csrc/vss_track.hip; vss_amd/track.py): a recursive tracker between perception
+ * and estimation.
+ *
+ * Every perceived 52-float row (the perception channel) is filtered in its own frame across calls -- predicted one
+ * control step with the project's drive model, then corrected with the new row by a fixed gain per kind of body,
+ * behind a position / velocity / heading gate -- in one launch per call.  vss_amd/track.py reference_track is the
+ * specification; the kernel equals it bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+#define VSS_TRACK_MAX_DELAY 15
+
+/* Where the rows lie, as vss_estimate_layout: strides in 52-float rows; the row of team block b, field f, robot k
+ * is b * team_stride + f * field_stride + k.  team_stride is read only with two teams.
+ *   SA, CMA: 1, -, 1, 1      DMA, opp_obs (N,3,52): 3, -, 3, 1      mirror: R, R N, R, 2
+ *   the blue rows of FULL's (N,2,3,52): 6, -, 3, 1 */
+typedef struct vss_track_layout {
+  int64_t field_stride;
+  int64_t team_stride;
+  int32_t robots;   /* 1 or 3 */
+  int32_t n_teams;  /* 1 or 2 */
+} vss_track_layout;
+
+/* The correction's gain per kind of body, each in [0, 1] (0: the kind is not filtered, its floats are the input's
+ * bit for bit), and the gates in the row's units (0: off). */
+typedef struct vss_track_params {
+  float gain_team;  /* the three own robots, which the drive model moves */
+  float gain_opp;   /* the three opponents, at constant velocity */
+  float gain_ball;  /* the ball, damped */
+  float gate_pos;   /* |z - p| in x or y beyond which a body is re-initialised from the input */
+  float gate_vel;   /* the same in vx or vy */
+} vss_track_params;
+
+/* One call of the channel, one launch.  obs, term: the perceived rows of call index `call` (term NULL: the start
+ * call -- every age 0, est = obs_out = obs, the ring's slot written).  State is the caller's, per row, packed
+ * (n_teams, n_fields, robots): est (rows, 52) the last filtered row; age int32, perception's recurrence saturating
+ * at delay; hist (delay, rows, 6) a ring of the row's own-action floats, call t in slot t % delay.  Per row, with
+ * its field's done:
+ *   a = clamp(age, 0, delay);  d = min(a + 1, delay);  age' = done ? 0 : d;  adv = 1 - (d - a)
+ *   cmd = delay == 0 ? term's own-action floats : hist[(call - d) % delay]
+ *   P = adv ? est moved one control step with cmd : est
+ *   term_out = update(P, term);  obs_out = done ? obs : update(P, obs)
+ *   est = obs_out;  age = age';  hist[call % delay] = obs's own-action floats
+ *
+ * VSS_E_ARG, before any HIP call: a null lay, prm, obs, done, est, age or obs_out; hist null with delay >= 1;
+ * exactly one of term / term_out null; a row pointer or est not 16-B, done or hist not 8-B or age not 4-B aligned;
+ * an output (obs_out, term_out, est, hist, age) whose byte range overlaps an input's or another output's; delay
+ * outside 0..VSS_TRACK_MAX_DELAY; a gain outside [0, 1] or not finite; a negative or non-finite gate; robots not 1
+ * or 3; n_teams not 1 or 2; field_stride < robots; with two teams a team_stride smaller than a block's span;
+ * done_stride < 1; n_fields < 0; sizes whose grid or byte offsets overflow.  n_fields == 0: VSS_OK, no launch. */
+int vss_track(void* stream, int64_t n_fields, const vss_track_layout* lay, const vss_track_params* prm, int32_t delay,
+              uint32_t call, const float* obs, const float* term, const int64_t* done, int64_t done_stride,
+              float* est, float* hist, int32_t* age, float* obs_out, float* term_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * The set plays (csrc/vss_setplay.hip; vss_amd/setplay.py): named restarts instead of the uniform drop.
+ *
+ * A share of the fields that finished an episode starts the next one from a named, table-driven placement -- a
+ * kickoff, a free ball, a penalty ... -- with jitter and mirroring instead of the step's uniform drop: one launch
+ * per call, after the step, over the step's own state and observation rows.  vss_amd/setplay.py reference_setplay
+ * is the specification; the kernel equals it bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+#define VSS_SETPLAY_MAX_PLAYS 8
+
+/* One entity's anchor (m, rad) and the half-widths of its uniform jitter.  Entities in order: the ball, blue 0..2,
+ * yellow 0..2; blue attacks +x.  The ball's yaw and r_yaw are not read. */
+typedef struct vss_setplay_entity { float x, y, yaw, r_pos, r_yaw; } vss_setplay_entity;
+
+/* A play: seven entities, the ball's velocity and its jitter, the cumulative weight up to and including this play
+ * (float32 running sum, computed on the host) and the probabilities of the two mirrorings. */
+typedef struct vss_setplay_play {
+  vss_setplay_entity e[7];
+  float ball_vx, ball_vy, r_vel, cum_weight, p_flip_x, p_flip_y;
+} vss_setplay_play;
+
+/* 1..VSS_SETPLAY_MAX_PLAYS plays; share in [0, 1]: the probability that a finished field is staged;
+ * total_weight == play[count - 1].cum_weight > 0. */
+typedef struct vss_setplay_table {
+  int32_t count;
+  float share, total_weight;
+  vss_setplay_play play[VSS_SETPLAY_MAX_PLAYS];
+} vss_setplay_table;
+
+/* Observation rows to rewrite for a placed field (the set plays' and the referee's), as vss_perceive_layout: strides
+ * in 52-float rows; the row of team block b, field f, robot k is obs + (b * team_stride + f * field_stride + k) * 52
+ * floats and is the view of robot k of team first_team + b.  team_stride is read with two teams only.
+ *   SA, CMA: 1, -, 1, 1, 0      DMA: 3, -, 3, 1, 0      opp_obs (N,3,52): 3, -, 3, 1, 1
+ *   mirror: R, R N, R, 2, 0     FULL's (N,2,3,52): 6, 3, 3, 2, 0 */
+typedef struct vss_setplay_view {
+  float* obs;
+  int64_t field_stride, team_stride;
+  int32_t robots, n_teams, first_team;
+} vss_setplay_view;
+
+/* One call, one launch.  Per field f that is done (done NULL: the start call, every field), with the draws of
+ * Philox4x32-10, key (seed lo, seed hi), counter (f, call, 10 << 24, block) -- see reference_setplay for the words:
+ *   staged = u_share < share;   k = the first play with u_play * total_weight < cum_weight
+ *   every entity at its anchor + (2u - 1) r, then flip_y (y, vy, yaw negated), then flip_x (the teams swapped,
+ *   x, vx negated, yaw -> pi - yaw), the yaw wrapped into [-pi, pi], (qz, qw) = sincos_small(yaw / 2)
+ * A staged field's 58 state channels (state is (58, n_fields), VSS_CH_*) and its rows in every view are written --
+ * the rows as vss_compute_observations gives them from that state with zero own-action floats -- chosen[f] = k and
+ * counts[k] += 1; every other field's state and rows stay and chosen[f] = -1.
+ *
+ * VSS_E_ARG, before any HIP call: a null tab or state; views null with n_views > 0; n_views outside 0..2;
+ * a view with a null obs, robots not 1 or 3, n_teams not 1 or 2, first_team + n_teams > 2, first_team < 0,
+ * field_stride < robots, or with two teams blocks that overlap (team_stride neither a block's span nor, with both
+ * teams inside one field stride as in FULL, robots <= team_stride <= field_stride - robots); obs not 16-B, done or counts
+ * not 8-B, state or chosen not 4-B aligned; done_stride < 1 with a done; n_fields < 0; sizes whose grid or byte
+ * offsets overflow; an output (state, a view's rows, counts, chosen) whose byte range overlaps done's or another
+ * output's; and a table that vss_amd/setplay.py Table.validate refuses: a count outside 1..8, a non-finite value, a
+ * share or flip probability outside [0, 1], cumulative weights that decrease, are negative or end at 0, or a
+ * total_weight that is not the last of them, |anchor yaw| > pi, r_yaw outside [0, pi], a negative radius, a robot
+ * with |x| + r_pos > 0.71 or |y| + r_pos > 0.61, a ball with |x| + r_pos > 0.75 or |y| + r_pos > 0.65, or two
+ * entities with |anchor distance| - sqrt(2) (r_i + r_j) < 0.08.  n_fields == 0: VSS_OK, no launch. */
+int vss_setplay(void* stream, int64_t n_fields, const vss_setplay_table* tab, uint64_t seed, uint32_t call,
+                const int64_t* done, int64_t done_stride, float* state, int32_t n_views,
+                const vss_setplay_view* views, int64_t* counts, int32_t* chosen);
+
+/* ---------------------------------------------------------------------------------------------
+ * The referee (csrc/vss_referee.hip; vss_amd/referee.py): stoppages inside an episode.
+ *
+ * Inside an episode a VSS match is stopped for a free ball (the ball is stuck), a penalty (two defenders in their own
+ * goal area with the ball) and a goal kick (two attackers in it), and restarts from the matching placement.  One launch
+ * per call, after the step and after the set plays, over the step's own state, dof velocities and observation rows:
+ * per field three counters are advanced and, where one reaches its threshold, the field is placed again from a table
+ * of three plays.  vss_amd/referee.py reference_referee is the specification; the kernel equals it bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+#define VSS_REFEREE_PLAYS 3   /* free ball, penalty, goal kick */
+#define VSS_REFEREE_CODES 8   /* verdict codes, the length of counts */
+
+/* A play: seven entities (vss_setplay_entity), the ball's velocity and its jitter; written as blue's own piece in the
+ * +y half. */
+typedef struct vss_referee_play { vss_setplay_entity e[7]; float ball_vx, ball_vy, r_vel; } vss_referee_play;
+
+/* play[0] the free ball, play[1] the penalty, play[2] the goal kick */
+typedef struct vss_referee_table { vss_referee_play play[3]; } vss_referee_table;
+
+/* stall_speed_sq: the ball counts as stuck while vx^2 + vy^2 is below it; area_x, area_y: a goal area is |x| > area_x
+ * and |y| < area_y; stall_steps, area_steps: the steps a condition must hold for a call (0: that call is off);
+ * max_stops: calls per episode (0: no cap). */
+typedef struct vss_referee_params {
+  float stall_speed_sq, area_x, area_y;
+  int32_t stall_steps, area_steps, max_stops;
+} vss_referee_params;
+
+/* One call, one launch.  counters is (n_fields, 4) int32: stall, defend, attack, stops.  views: the rows to rewrite for
+ * a whistled field, as vss_setplay's.  Per field f:
+ *   done (done NULL: no field is done): the four counters = 0, verdict[f] = -1, nothing else is touched.
+ *   otherwise, with the ball (bx, by, bvx, bvy) and the robots' positions of state (58, n_fields), VSS_CH_*:
+ *     stall  = bvx^2 + bvy^2 < stall_speed_sq ? min(stall + 1, 1 << 30) : 0
+ *     in_area = |bx| > area_x && |by| < area_y;  side = bx < 0 ? 0 : 1  (0: blue's own area);  a robot is inside
+ *     when |x| > area_x && |y| < area_y && (x < 0) == (bx < 0);  def_n, att_n: the defending and the attacking
+ *     team's robots inside
+ *     defend = in_area && def_n >= 2 ? min(defend + 1, 1 << 30) : 0;  attack likewise with att_n
+ *     while max_stops == 0 || stops < max_stops, the first that holds:
+ *       area_steps > 0 && defend >= area_steps: a penalty for the attacking team   code 4 (blue's, side 1), 5
+ *       area_steps > 0 && attack >= area_steps: a goal kick for the defending team code 6 (blue's, side 0), 7
+ *       stall_steps > 0 && stall >= stall_steps: a free ball  code 0 (bx >= 0, by >= 0), 1 (by < 0), 2 (bx < 0), 3
+ *   A whistled field is placed from its play as vss_setplay places one -- anchor + (2u - 1) r per entity, flip_y, then
+ *   flip_x with the role swap, the yaw wrapped, (qz, qw) = sincos_small(yaw / 2) -- with the flips decided by the
+ *   verdict (free ball: flip_x = bx < 0, flip_y = by < 0; penalty: flip_x = code 5; goal kick: flip_x = code 7,
+ *   flip_y = by < 0) and the draws of Philox4x32-10, key (seed lo, seed hi), counter (f, call, 11 << 24, 1 + e) for
+ *   entity e.  Written: its 58 state channels (robot velocities and yaw rates 0), its twelve floats of dof_vel
+ *   (n_fields, 2, 3, 2) = +0.0, its rows in every view (own-action floats +0.0), stall = defend = attack = 0,
+ *   stops += 1, verdict[f] = code, counts[code] += 1.  Every other field keeps its state, dof_vel and rows, gets its
+ *   counters stored and verdict[f] = -1.
+ *
+ * VSS_E_ARG, before any HIP call: a null tab, prm, state, dof_vel or counters; views null with n_views > 0;
+ * n_views outside 0..2; a view with a null obs, robots not 1 or 3, n_teams not 1 or 2, first_team + n_teams > 2,
+ * first_team < 0, field_stride < robots, or with two teams blocks that overlap (team_stride neither a block's span
+ * nor, with both teams inside one field stride as in FULL, robots <= team_stride <= field_stride - robots); obs,
+ * dof_vel or counters not 16-B, done or counts not 8-B, state or verdict not 4-B aligned; done_stride < 1 with a done;
+ * n_fields < 0; sizes whose grid or byte offsets overflow; an output (state, dof_vel, counters, a view's rows, counts,
+ * verdict) whose byte range overlaps done's or another output's; parameters that vss_amd/referee.py Params.validate
+ * refuses: a negative stall_steps, area_steps or max_stops, a stall_speed_sq that is negative or not finite, area_x
+ * outside (0, 0.75), area_y outside (0, 0.65]; and a table that vss_amd/referee.py RefTable.validate refuses: per play
+ * every entity rule of vss_setplay's table (a non-finite value, |anchor yaw| > pi, r_yaw outside [0, pi], a negative
+ * radius, a robot with |x| + r_pos > 0.71 or |y| + r_pos > 0.61, a ball with |x| + r_pos > 0.75 or |y| + r_pos > 0.65,
+ * two entities with |anchor distance| - sqrt(2) (r_i + r_j) < 0.08), and a free-ball or penalty play whose ball can
+ * lie inside a goal area (|x| + r_pos > area_x and |y| - r_pos < area_y).  n_fields == 0: VSS_OK, no launch. */
+int vss_referee(void* stream, int64_t n_fields, const vss_referee_table* tab, const vss_referee_params* prm,
+                uint64_t seed, uint32_t call, const int64_t* done, int64_t done_stride, float* state, float* dof_vel,
+                int32_t* counters, int32_t n_views, const vss_setplay_view* views, int64_t* counts, int32_t* verdict);
+
 #ifdef __cplusplus
 }
 #endif

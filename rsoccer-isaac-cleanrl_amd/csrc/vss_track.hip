@@ -1,4 +1,4 @@
-// vss_track.hip — the tracking channel in one launch (gfx950): vss_track of include/vss_track.h.
+// vss_track.hip — the tracking channel in one launch (gfx950): vss_track of include/vss.h.
 //
 // Every perceived observation row is filtered across calls in its own frame: the last filtered row (`est`, the
 // caller's state) is moved one control step with the project's drive model and the command that moved that frame,
@@ -8,10 +8,10 @@
 // rounded, denormals kept, no FMA contraction (-ffp-contract=off and the pragma below).  The result equals the
 // reference bit for bit (tests/test_track_gpu.py).
 //
-//   The one-step drive model below (drive, move, turn, the ball's damping) restates csrc/vss_estimate.hip's: this
-//   unit cannot share a header with the core, whose stamped file list is closed.  In Python there is one copy
-//   (reference_track calls estimate.predict_rows) and the bit-equality test pins this restatement to it.  Folding
-//   the unit into the core library removes the duplicate.
+//   The one-step drive model below (drive, move, turn, the ball's damping) restates vss_estimate.hip's: it
+//   was written when this unit was a library of its own.  In Python there is one copy (reference_track calls
+//   estimate.predict_rows) and the bit-equality test pins this restatement to it.  Now that both are units of one
+//   library a shared header can remove the duplicate; that is not done yet.
 //
 //   one row per lane, as vss_estimate.hip: est, age and hist are per row, so a lane reads and writes only its own
 //   state, nothing goes through LDS and the workgroup shape (256 rows, four waves) is free of the layout.
@@ -29,8 +29,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/vss_track.h"
-#include "../csrc/vss_numerics.h"
+#include "../../include/vss.h"
+#include "vss_numerics.h"
 
 #pragma clang fp contract(off)
 
@@ -253,24 +253,22 @@ inline bool gate_ok(float g) { return g >= 0.0f && g <= 3.4028235e38f; }   // fa
 
 extern "C" {
 
-int vss_track_abi_version(void) { return VSS_TRACK_ABI_VERSION; }
-
 int vss_track(void* stream, int64_t n_fields, const vss_track_layout* lay, const vss_track_params* prm, int32_t delay,
               uint32_t call, const float* obs, const float* term, const int64_t* done, int64_t done_stride, float* est,
               float* hist, int32_t* age, float* obs_out, float* term_out) {
   using namespace vtrk;
-  if (!lay || !prm || !obs || !done || !est || !age || !obs_out) return VSS_TRACK_E_ARG;
-  if (delay < 0 || delay > VSS_TRACK_MAX_DELAY) return VSS_TRACK_E_ARG;
-  if (delay >= 1 && !hist) return VSS_TRACK_E_ARG;
-  if ((term == nullptr) != (term_out == nullptr)) return VSS_TRACK_E_ARG;
+  if (!lay || !prm || !obs || !done || !est || !age || !obs_out) return VSS_E_ARG;
+  if (delay < 0 || delay > VSS_TRACK_MAX_DELAY) return VSS_E_ARG;
+  if (delay >= 1 && !hist) return VSS_E_ARG;
+  if ((term == nullptr) != (term_out == nullptr)) return VSS_E_ARG;
   if (!gain_ok(prm->gain_team) || !gain_ok(prm->gain_opp) || !gain_ok(prm->gain_ball) || !gate_ok(prm->gate_pos) ||
       !gate_ok(prm->gate_vel))
-    return VSS_TRACK_E_ARG;
+    return VSS_E_ARG;
   if (misaligned(obs, 16) || misaligned(term, 16) || misaligned(obs_out, 16) || misaligned(term_out, 16) ||
       misaligned(est, 16) || misaligned(done, 8) || misaligned(hist, 8) || misaligned(age, 4))
-    return VSS_TRACK_E_ARG;
-  if ((lay->robots != 1 && lay->robots != 3) || (lay->n_teams != 1 && lay->n_teams != 2)) return VSS_TRACK_E_ARG;
-  if (n_fields < 0 || done_stride < 1 || lay->field_stride < lay->robots) return VSS_TRACK_E_ARG;
+    return VSS_E_ARG;
+  if ((lay->robots != 1 && lay->robots != 3) || (lay->n_teams != 1 && lay->n_teams != 2)) return VSS_E_ARG;
+  if (n_fields < 0 || done_stride < 1 || lay->field_stride < lay->robots) return VSS_E_ARG;
   // the pointer-equality part of the aliasing rule holds at any size
   {
     const void* outs[5] = {obs_out, term_out, est, hist, age};
@@ -278,25 +276,25 @@ int vss_track(void* stream, int64_t n_fields, const vss_track_layout* lay, const
     for (int i = 0; i < 5; ++i) {
       if (!outs[i]) continue;
       for (int j = 0; j < 3; ++j)
-        if (outs[i] == ins[j]) return VSS_TRACK_E_ARG;
+        if (outs[i] == ins[j]) return VSS_E_ARG;
       for (int j = i + 1; j < 5; ++j)
-        if (outs[i] == outs[j]) return VSS_TRACK_E_ARG;
+        if (outs[i] == outs[j]) return VSS_E_ARG;
     }
   }
-  if (n_fields == 0) return VSS_TRACK_OK;
+  if (n_fields == 0) return VSS_OK;
 
   const int64_t R = (int64_t)lay->robots * lay->n_teams;
   // sizes: the grid is an unsigned x dimension; every byte offset stays an int64 (208 B per row, a ring of up to 15)
   const int64_t kMaxRows = INT64_MAX / (4 * kObs) / (VSS_TRACK_MAX_DELAY + 1);
   const int64_t m = n_fields - 1;
   if (n_fields > kMaxRows / R || lay->field_stride > kMaxRows / n_fields || done_stride > (INT64_MAX / 8) / n_fields)
-    return VSS_TRACK_E_ARG;
+    return VSS_E_ARG;
   const int64_t block_rows = m * lay->field_stride + lay->robots;  // rows one team block spans
   if (lay->n_teams == 2 && (lay->team_stride < block_rows || lay->team_stride > kMaxRows - block_rows))
-    return VSS_TRACK_E_ARG;
+    return VSS_E_ARG;
   const int64_t rows = n_fields * R;
   const int64_t blocks = rows / kBlock + (rows % kBlock != 0);
-  if (blocks > INT32_MAX) return VSS_TRACK_E_ARG;
+  if (blocks > INT32_MAX) return VSS_E_ARG;
   const uint64_t span = (uint64_t)((lay->n_teams == 2 ? lay->team_stride : 0) + block_rows) * kObs * 4;
   const uint64_t est_b = (uint64_t)rows * kObs * 4, hist_b = (uint64_t)delay * (uint64_t)rows * 24;
   const uint64_t age_b = (uint64_t)rows * 4, done_b = (uint64_t)(m * done_stride + 1) * 8;
@@ -307,9 +305,9 @@ int vss_track(void* stream, int64_t n_fields, const vss_track_layout* lay, const
   const uint64_t in_b[3] = {span, span, done_b};
   for (int i = 0; i < 5; ++i) {
     for (int j = 0; j < 3; ++j)
-      if (overlap(outs[i], out_b[i], ins[j], in_b[j])) return VSS_TRACK_E_ARG;
+      if (overlap(outs[i], out_b[i], ins[j], in_b[j])) return VSS_E_ARG;
     for (int j = i + 1; j < 5; ++j)
-      if (overlap(outs[i], out_b[i], outs[j], out_b[j])) return VSS_TRACK_E_ARG;
+      if (overlap(outs[i], out_b[i], outs[j], out_b[j])) return VSS_E_ARG;
   }
 
   Args a;
@@ -324,7 +322,7 @@ int vss_track(void* stream, int64_t n_fields, const vss_track_layout* lay, const
   hipStream_t s = (hipStream_t)stream;
   if (lay->robots == 1) hipLaunchKernelGGL((track_kernel<1>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((track_kernel<3>), grid, block, 0, s, a);
-  return hipGetLastError() == hipSuccess ? VSS_TRACK_OK : VSS_TRACK_E_LAUNCH;
+  return hipGetLastError() == hipSuccess ? VSS_OK : VSS_E_LAUNCH;
 }
 
 }  // extern "C"

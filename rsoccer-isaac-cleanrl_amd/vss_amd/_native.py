@@ -9,9 +9,11 @@ streams.
 
 Nothing of the ABI is written down here: the header is parsed at import (vss_amd/cheader.py), and
   - every `#define VSS_<NAME> <integer>` is the module constant <NAME> (ABI_VERSION, MODE_SA, CH_RX, STATE_CHANNELS,
-    MAX_ACTOR_GROUPS, PERCEIVE_MAX_DELAY, ACTUATE_MAX_LEVELS, ESTIMATE_MAX_DELAY, ...);
+    MAX_ACTOR_GROUPS, PERCEIVE_MAX_DELAY, ACTUATE_MAX_LEVELS, ESTIMATE_MAX_DELAY, TRACK_MAX_DELAY, SETPLAY_MAX_PLAYS,
+    REFEREE_CODES, ...);
   - every `typedef struct vss_<name>` is a ctypes.Structure in camel case with "IO" for "io" (vss_params -> VssParams,
-    vss_step_io -> VssStepIO, vss_actuate_params -> VssActuateParams, ...), pointer members as c_void_p;
+    vss_step_io -> VssStepIO, vss_actuate_params -> VssActuateParams, vss_setplay_view -> VssSetplayView, ...), pointer
+    members as c_void_p;
   - EXPORTED is the prototypes' names and bind() sets their restype / argtypes on a library.
 The files the library's source stamp covers are likewise read from csrc/Makefile's STAMPED line.
 """
@@ -56,15 +58,14 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "vss.h"
 REBUILD = "`make -C {csrc}` or `python -c 'import __graft_entry__ as g; g.build()'`"
 
 
-def _stamped(csrc: str | None = None) -> tuple:
+def _stamped() -> tuple:
     """The files csrc/Makefile stamps into libvss_amd.so, in its order: the words of its STAMPED line, each without
-    the ":<flag set>" a translation unit carries there.  (`csrc`: another unit's directory, e.g. csrc_track.)"""
-    csrc = CSRC if csrc is None else csrc
-    with open(os.path.join(csrc, "Makefile")) as f:
+    the ":<flag set>" a translation unit carries there."""
+    with open(os.path.join(CSRC, "Makefile")) as f:
         line = re.search(r"^STAMPED\s*:?=\s*(\S.*)$", f.read(), re.M)
     if not line:
-        raise NativeError(f"{csrc}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
-    return tuple(os.path.normpath(os.path.join(csrc, word.split(":")[0])) for word in line.group(1).split())
+        raise NativeError(f"{CSRC}/Makefile has no STAMPED line: the library's source stamp cannot be checked")
+    return tuple(os.path.normpath(os.path.join(CSRC, word.split(":")[0])) for word in line.group(1).split())
 
 
 STAMPED = _stamped()
@@ -79,10 +80,10 @@ globals().update({"".join("IO" if part == "io" else part.capitalize() for part i
 _lib = None
 
 
-def source_hash(stamped: tuple | None = None) -> str:
-    """sha256 (first 16 hex digits) of the stamped sources as they are in this tree (`stamped`: another unit's)."""
+def source_hash() -> str:
+    """sha256 (first 16 hex digits) of the stamped sources as they are in this tree."""
     h = hashlib.sha256()
-    for path in STAMPED if stamped is None else stamped:
+    for path in STAMPED:
         with open(path, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

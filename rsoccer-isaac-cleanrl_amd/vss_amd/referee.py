@@ -1,4 +1,4 @@
-"""The referee (include/vss_referee.h `vss_referee`, csrc_referee/vss_referee.hip).
+"""The referee (include/vss.h `vss_referee`, csrc/vss_referee.hip).
 
 Set plays (setplay.py) start an episode from a real match's restarts; inside an episode nothing was ever whistled.  The
 referee calls three things mid-episode: a free ball when the ball has been stuck for `stall_steps` steps, a penalty when
@@ -30,9 +30,9 @@ Per call t and field f, with counters (n, 4) int32 = stall, defend, attack, stop
     written: the 58 state channels, dof_vel's twelve floats +0.0, the rows of every view (own-action floats +0.0),
         stall = defend = attack = 0, stops += 1, verdict[f] = code, counts[code] += 1
 
-The library is a unit of its own beside libvss_amd.so, bound from include/vss_referee.h with vss_amd/cheader.py and
-checked against csrc_referee/Makefile's STAMPED files, as setplay.py does.  There is no fallback: a missing or stale
-library raises.
+The entry point is libvss_amd.so's, bound from include/vss.h by vss_amd/_native.py like every other: the structs, the
+constants and the loader here are `_native`'s under the module's own names, and the views and entities are the set
+plays' (one struct each in the header).  There is no fallback: a missing or stale library raises.
 """
 from __future__ import annotations
 
@@ -45,7 +45,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import channel, cheader
+from . import channel
 from . import setplay as S
 from .perceive import NUM_OBS, _philox, _sincos_small
 # View and the view_* constructors are the set plays' own, re-exported: the two units rewrite the same rows
@@ -55,23 +55,13 @@ from .setplay import (CH_RQW, CH_RQX, CH_RQY, CH_RQZ, CH_RVX, CH_RVY, CH_RW, CH_
 F = np.float32
 U32 = np.uint32
 
-# ---- the library ----------------------------------------------------------------------------------------------------
-CSRC = os.path.join(os.path.dirname(N.HERE), "csrc_referee")
-HEADER = os.path.join(os.path.dirname(N.HEADER), "vss_referee.h")
-LIB_PATH = os.path.join(N.HERE, "libvss_referee.so")
-STAMPED = N._stamped(CSRC)
-
-with open(HEADER) as _f:
-    ABI = cheader.parse(_f.read())
-EXPORTED = tuple(ABI.functions)
-ABI_VERSION = ABI.constants["VSS_REFEREE_ABI_VERSION"]
-CODES = ABI.constants["VSS_REFEREE_CODES"]
-VssRefereeEntity = ABI.structs["vss_referee_entity"]
-VssRefereePlay = ABI.structs["vss_referee_play"]
-VssRefereeTable = ABI.structs["vss_referee_table"]
-VssRefereeParams = ABI.structs["vss_referee_params"]
-VssRefereeView = ABI.structs["vss_referee_view"]
-ERRORS = {ABI.constants["VSS_REFEREE_E_ARG"]: "bad argument", ABI.constants["VSS_REFEREE_E_LAUNCH"]: "kernel launch failed"}
+CODES = N.REFEREE_CODES
+VssRefereePlay = N.VssRefereePlay
+VssRefereeTable = N.VssRefereeTable
+VssRefereeParams = N.VssRefereeParams
+VssRefereeEntity = S.VssSetplayEntity  # the header has one entity and one view struct: the set plays'
+VssRefereeView = S.VssSetplayView
+load = N.load  # the one library's loader under the module's own name, as before
 
 PURPOSE = 11          # the Philox counter's purpose byte (the step 0..6, perception 7, actuation 8 and 9, set plays 10)
 CAP = 1 << 30         # a counter stops counting here
@@ -80,58 +70,9 @@ PLAYS = ("free_ball", "penalty", "goal_kick")  # the table's three plays, by the
 RECORD = {"free_ball": (0, 1, 2, 3), "penalty_for": (4,), "penalty_against": (5,), "goal_kick_for": (6,),
           "goal_kick_against": (7,)}
 
-_lib = None
-
-
-def source_hash() -> str:
-    """sha256 (first 16 hex digits) of the unit's stamped sources as they are in this tree."""
-    return N.source_hash(STAMPED)
-
-
-def verify_source_hash(lib: ctypes.CDLL, expected: str | None = None) -> None:
-    """Raise unless the library was built from the tree's sources."""
-    want = source_hash() if expected is None else expected
-    try:
-        fn = lib.vss_referee_source_hash
-    except AttributeError:
-        built = "<no vss_referee_source_hash symbol>"
-    else:
-        fn.restype = ctypes.c_char_p
-        built = fn().decode()
-    if built != want:
-        raise N.NativeError(f"{LIB_PATH} was built from other sources (stamp {built}, tree {want}); rebuild it with "
-                            + N.REBUILD.format(csrc=N.CSRC))
-
-
-def load() -> ctypes.CDLL:
-    """Load libvss_referee.so (raises if it has not been built, or was built from other sources)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise N.NativeError(f"the referee's library was not found at {LIB_PATH}; build it with "
-                            + N.REBUILD.format(csrc=N.CSRC))
-    lib = ctypes.CDLL(LIB_PATH)
-    verify_source_hash(lib)
-    try:
-        cheader.bind(lib, ABI)
-    except AttributeError as e:
-        raise N.NativeError(f"{LIB_PATH} lacks an entry point that {HEADER} declares: {e}") from None
-    built = lib.vss_referee_abi_version()
-    if built != ABI_VERSION:
-        raise N.NativeError(f"libvss_referee ABI {built} != expected {ABI_VERSION}")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str = "vss_referee") -> None:
-    if rc != 0:
-        raise N.NativeError(f"{what} failed: {ERRORS.get(rc, 'unknown error')} (code {rc})")
-
-
 # ---- parameters and the table -------------------------------------------------------------------------------------------
 class Params(NamedTuple):
-    """include/vss_referee.h vss_referee_params, in its order.  `of` builds one from a speed, a depth and a width."""
+    """include/vss.h vss_referee_params, in its order.  `of` builds one from a speed, a depth and a width."""
     stall_speed_sq: float = float(F(0.05) * F(0.05))
     area_x: float = 0.60
     area_y: float = 0.35
@@ -152,7 +93,7 @@ class Params(NamedTuple):
         return self.stall_steps > 0 or self.area_steps > 0
 
     def validate(self) -> "Params":
-        """ValueError for what vss_referee refuses with VSS_REFEREE_E_ARG (in double on the float32 values)."""
+        """ValueError for what vss_referee refuses with VSS_E_ARG (in double on the float32 values)."""
         for name in ("stall_steps", "area_steps", "max_stops"):
             v = getattr(self, name)
             if int(v) != v or not 0 <= int(v) < 2 ** 31:
@@ -435,7 +376,7 @@ class Referee(channel.Channel):
                                 self.seed, self.call_index & 0xFFFFFFFF, N.ptr(done), 1, env_state.data_ptr(),
                                 dof_vel.data_ptr(), self.counters.data_ptr(), n_views, arr, self.counts.data_ptr(),
                                 self.verdict.data_ptr())
-        check(rc)
+        N.check(rc, "vss_referee")
         self.call_index += 1
 
     def restart(self, call_index: int = 0) -> None:

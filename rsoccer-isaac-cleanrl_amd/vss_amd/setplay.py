@@ -1,4 +1,4 @@
-"""Set plays (include/vss_setplay.h `vss_setplay`, csrc_setplay/vss_setplay.hip).
+"""Set plays (include/vss.h `vss_setplay`, csrc/vss_setplay.hip).
 
 The step starts every episode with a uniform drop of the seven bodies (envs/vss.py:267-333).  A VSS match restarts
 from a kickoff, one of four free-ball marks, a penalty or a goal kick, with the robots in formation -- situations a
@@ -36,8 +36,8 @@ chosen[f] = k and counts[k] += 1; every other field's state and rows stay and ch
 Table.validate guarantees that no play can start in contact (worst-case pair distance >= 0.08 m, K_RR_DIST, above the
 uniform reset's own 0.07 m rule) or outside the walls, so there is no rejection loop.
 
-The library is a unit of its own beside libvss_amd.so, bound from include/vss_setplay.h with vss_amd/cheader.py and
-checked against csrc_setplay/Makefile's STAMPED files, as track.py does.  There is no fallback: a missing or stale
+The entry point is libvss_amd.so's, bound from include/vss.h by vss_amd/_native.py like every other: the structs, the
+constants and the loader here are `_native`'s under the module's own names.  There is no fallback: a missing or stale
 library raises.
 """
 from __future__ import annotations
@@ -52,28 +52,18 @@ import numpy as np
 import torch
 
 from . import _native as N
-from . import channel, cheader
+from . import channel
 from .perceive import NUM_OBS, _philox, _sincos_small, _u01
 
 F = np.float32
 U32 = np.uint32
 
-# ---- the library ----------------------------------------------------------------------------------------------------
-CSRC = os.path.join(os.path.dirname(N.HERE), "csrc_setplay")
-HEADER = os.path.join(os.path.dirname(N.HEADER), "vss_setplay.h")
-LIB_PATH = os.path.join(N.HERE, "libvss_setplay.so")
-STAMPED = N._stamped(CSRC)
-
-with open(HEADER) as _f:
-    ABI = cheader.parse(_f.read())
-EXPORTED = tuple(ABI.functions)
-ABI_VERSION = ABI.constants["VSS_SETPLAY_ABI_VERSION"]
-MAX_PLAYS = ABI.constants["VSS_SETPLAY_MAX_PLAYS"]
-VssSetplayEntity = ABI.structs["vss_setplay_entity"]
-VssSetplayPlay = ABI.structs["vss_setplay_play"]
-VssSetplayTable = ABI.structs["vss_setplay_table"]
-VssSetplayView = ABI.structs["vss_setplay_view"]
-ERRORS = {ABI.constants["VSS_SETPLAY_E_ARG"]: "bad argument", ABI.constants["VSS_SETPLAY_E_LAUNCH"]: "kernel launch failed"}
+MAX_PLAYS = N.SETPLAY_MAX_PLAYS
+VssSetplayEntity = N.VssSetplayEntity
+VssSetplayPlay = N.VssSetplayPlay
+VssSetplayTable = N.VssSetplayTable
+VssSetplayView = N.VssSetplayView
+load = N.load  # the one library's loader under the module's own name, as before
 
 PURPOSE = 10          # the Philox counter's purpose byte (the step 0..6, perception 7, actuation 8 and 9)
 BLOCKS = 8            # Philox blocks per staged field: control, the ball, six robots
@@ -85,55 +75,6 @@ HALF_BALL = (0.75, 0.65)
 # include/vss.h VSS_CH_*
 CH_RX, CH_RY, CH_RQX, CH_RQY, CH_RQZ, CH_RQW, CH_RVX, CH_RVY, CH_RW = (N.CH_RX, N.CH_RY, N.CH_RQX, N.CH_RQY, N.CH_RQZ,
                                                                       N.CH_RQW, N.CH_RVX, N.CH_RVY, N.CH_RW)
-
-_lib = None
-
-
-def source_hash() -> str:
-    """sha256 (first 16 hex digits) of the unit's stamped sources as they are in this tree."""
-    return N.source_hash(STAMPED)
-
-
-def verify_source_hash(lib: ctypes.CDLL, expected: str | None = None) -> None:
-    """Raise unless the library was built from the tree's sources."""
-    want = source_hash() if expected is None else expected
-    try:
-        fn = lib.vss_setplay_source_hash
-    except AttributeError:
-        built = "<no vss_setplay_source_hash symbol>"
-    else:
-        fn.restype = ctypes.c_char_p
-        built = fn().decode()
-    if built != want:
-        raise N.NativeError(f"{LIB_PATH} was built from other sources (stamp {built}, tree {want}); rebuild it with "
-                            + N.REBUILD.format(csrc=N.CSRC))
-
-
-def load() -> ctypes.CDLL:
-    """Load libvss_setplay.so (raises if it has not been built, or was built from other sources)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise N.NativeError(f"the set plays' library was not found at {LIB_PATH}; build it with "
-                            + N.REBUILD.format(csrc=N.CSRC))
-    lib = ctypes.CDLL(LIB_PATH)
-    verify_source_hash(lib)
-    try:
-        cheader.bind(lib, ABI)
-    except AttributeError as e:
-        raise N.NativeError(f"{LIB_PATH} lacks an entry point that {HEADER} declares: {e}") from None
-    built = lib.vss_setplay_abi_version()
-    if built != ABI_VERSION:
-        raise N.NativeError(f"libvss_setplay ABI {built} != expected {ABI_VERSION}")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str = "vss_setplay") -> None:
-    if rc != 0:
-        raise N.NativeError(f"{what} failed: {ERRORS.get(rc, 'unknown error')} (code {rc})")
-
 
 # ---- plays and tables -------------------------------------------------------------------------------------------------
 class Play(NamedTuple):
@@ -148,7 +89,7 @@ class Play(NamedTuple):
 
 
 class View(NamedTuple):
-    """Observation rows to rewrite (include/vss_setplay.h vss_setplay_view), strides in 52-float rows."""
+    """Observation rows to rewrite (include/vss.h vss_setplay_view), strides in 52-float rows."""
     field_stride: int
     team_stride: int = 0
     robots: int = 1
@@ -211,7 +152,7 @@ class Table:
         return cum
 
     def validate(self) -> "Table":
-        """ValueError for what vss_setplay refuses with VSS_SETPLAY_E_ARG (the same rules, in double on the float32
+        """ValueError for what vss_setplay refuses with VSS_E_ARG (the same rules, in double on the float32
         values the kernel gets)."""
         if not 1 <= len(self.plays) <= MAX_PLAYS:
             raise ValueError(f"set plays: a table holds 1..{MAX_PLAYS} plays, got {len(self.plays)}")
@@ -538,7 +479,7 @@ class Stager(channel.Channel):
         rc = load().vss_setplay(N.stream_of(self.device), self.n_fields, ctypes.byref(tab), self.seed,
                                 self.call & 0xFFFFFFFF, N.ptr(done), 1, env_state.data_ptr(), n_views, arr,
                                 self.counts.data_ptr(), self.chosen.data_ptr())
-        check(rc)
+        N.check(rc, "vss_setplay")
         self.call += 1
 
     @torch.no_grad()

@@ -1,4 +1,4 @@
-"""The tracking channel (include/vss_track.h `vss_track`, csrc_track/vss_track.hip).
+"""The tracking channel (include/vss.h `vss_track`, csrc/vss_track.hip).
 
 No VSS team feeds single camera frames to its controller: it runs a recursive tracker that predicts with a motion
 model and corrects with the new frame.  The perception channel (vss_amd/perceive.py) delivers rows that are late and
@@ -26,89 +26,30 @@ adv is 0 while perception re-delivers an episode's first frame (the update then 
 age is saturated, which needs D calls since the episode's first: the slot read was written by the episode's second
 call at the earliest, so no command of an earlier episode is ever used.
 
-The library is a unit of its own beside libvss_amd.so: this module binds it from include/vss_track.h with
-vss_amd/cheader.py and checks its source stamp against csrc_track/Makefile's STAMPED files, as _native.py does for
-the core.  There is no fallback: a missing or stale library raises.
+The entry point is libvss_amd.so's, bound from include/vss.h by vss_amd/_native.py like every other: the structs, the
+constants and the loader here are `_native`'s under the module's own names.  There is no fallback: a missing or stale
+library raises.
 """
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _native as N
-from . import channel, cheader
+from . import channel
 from . import estimate as _E
 from .estimate import OPPONENTS, OWN
 from .perceive import ACTION_FLOATS, NUM_OBS, _sincos_small
 
 F = np.float32
 
-# ---- the library ----------------------------------------------------------------------------------------------------
-CSRC = os.path.join(os.path.dirname(N.HERE), "csrc_track")
-HEADER = os.path.join(os.path.dirname(N.HEADER), "vss_track.h")
-LIB_PATH = os.path.join(N.HERE, "libvss_track.so")
-STAMPED = N._stamped(CSRC)
-
-with open(HEADER) as _f:
-    ABI = cheader.parse(_f.read())
-EXPORTED = tuple(ABI.functions)
-ABI_VERSION = ABI.constants["VSS_TRACK_ABI_VERSION"]
-MAX_DELAY = ABI.constants["VSS_TRACK_MAX_DELAY"]
-VssTrackLayout = ABI.structs["vss_track_layout"]
-VssTrackParams = ABI.structs["vss_track_params"]
-ERRORS = {ABI.constants["VSS_TRACK_E_ARG"]: "bad argument", ABI.constants["VSS_TRACK_E_LAUNCH"]: "kernel launch failed"}
-
-_lib = None
-
-
-def source_hash() -> str:
-    """sha256 (first 16 hex digits) of the unit's stamped sources as they are in this tree."""
-    return N.source_hash(STAMPED)
-
-
-def verify_source_hash(lib: ctypes.CDLL, expected: str | None = None) -> None:
-    """Raise unless the library was built from the tree's sources."""
-    want = source_hash() if expected is None else expected
-    try:
-        fn = lib.vss_track_source_hash
-    except AttributeError:
-        built = "<no vss_track_source_hash symbol>"
-    else:
-        fn.restype = ctypes.c_char_p
-        built = fn().decode()
-    if built != want:
-        raise N.NativeError(f"{LIB_PATH} was built from other sources (stamp {built}, tree {want}); rebuild it with "
-                            + N.REBUILD.format(csrc=N.CSRC))
-
-
-def load() -> ctypes.CDLL:
-    """Load libvss_track.so (raises if it has not been built, or was built from other sources)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise N.NativeError(f"the tracking channel's library was not found at {LIB_PATH}; build it with "
-                            + N.REBUILD.format(csrc=N.CSRC))
-    lib = ctypes.CDLL(LIB_PATH)
-    verify_source_hash(lib)
-    try:
-        cheader.bind(lib, ABI)
-    except AttributeError as e:
-        raise N.NativeError(f"{LIB_PATH} lacks an entry point that {HEADER} declares: {e}") from None
-    built = lib.vss_track_abi_version()
-    if built != ABI_VERSION:
-        raise N.NativeError(f"libvss_track ABI {built} != expected {ABI_VERSION}")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str = "vss_track") -> None:
-    if rc != 0:
-        raise N.NativeError(f"{what} failed: {ERRORS.get(rc, 'unknown error')} (code {rc})")
+MAX_DELAY = N.TRACK_MAX_DELAY
+VssTrackLayout = N.VssTrackLayout
+VssTrackParams = N.VssTrackParams
+load = N.load  # the one library's loader under the module's own name, as before
 
 
 # ---- layouts and parameters -------------------------------------------------------------------------------------------
@@ -285,7 +226,7 @@ class TrackingChannel(channel.Channel):
             self.call & 0xFFFFFFFF, obs.data_ptr(), N.ptr(term), done.data_ptr(), self.done_stride, self.est.data_ptr(),
             self.hist.data_ptr() if self.delay else None, self.age.data_ptr(), self.obs_out.data_ptr(),
             None if term is None else self.term_out.data_ptr())
-        check(rc)
+        N.check(rc, "vss_track")
         self.call += 1
 
     @torch.no_grad()

@@ -26,33 +26,33 @@ def library_symbols():
 
 
 def test_header_declares_the_expected_entry_points():
-    """The header's prototypes are the library's exported functions, all 63 of them, each once; EXPORTED is that list."""
+    """The header's prototypes are the library's exported functions, all 66 of them, each once; EXPORTED is that list."""
     with open(N.HEADER) as f:
         text = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     names = re.findall(r"\b(vss_\w+)\s*\(", text)  # every name in front of a parenthesis, not through the parser
-    assert len(names) == len(set(names)) == 63
-    assert sorted(names) == declared_functions() == sorted(N.EXPORTED) and len(N.EXPORTED) == 63
+    assert len(names) == len(set(names)) == 66
+    assert sorted(names) == declared_functions() == sorted(N.EXPORTED) and len(N.EXPORTED) == 66
     lib = N.load()
     for name in names:
         assert hasattr(lib, name), name
     if shutil.which("nm"):
         assert library_symbols() == sorted(names)
     for name in ("vss_step", "vss_step_mirror", "vss_gae", "vss_scripted_team", "vss_perceive", "vss_actuate",
-                 "vss_estimate", "vss_linear_tanh_loss_bf16x6"):
+                 "vss_estimate", "vss_track", "vss_setplay", "vss_referee", "vss_linear_tanh_loss_bf16x6"):
         assert name in N.EXPORTED, name
 
 
 def test_stamped_is_the_makefiles_list():
-    """N.STAMPED is csrc/Makefile's STAMPED line, in its order: the eleven kernel sources, the shared row header, the
-    shared numerics header, the ABI header and the Makefile itself."""
+    """N.STAMPED is csrc/Makefile's STAMPED line, in its order: the fourteen kernel sources, the shared row header, the
+    shared numerics header, the shared placement header, the ABI header and the Makefile itself."""
     with open(os.path.join(N.CSRC, "Makefile")) as f:
         (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
     files = [w.split(":")[0] for w in line.split()]
     assert list(N.STAMPED) == [os.path.normpath(os.path.join(N.CSRC, w)) for w in files]
     assert [os.path.basename(p) for p in N.STAMPED] == [
         "vss_step.hip", "vss_update.hip", "vss_policy.hip", "vss_gemm_x6.hip", "vss_loss.hip", "vss_optim.hip",
-        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_actuate.hip", "vss_estimate.hip", "vss_loss_row.h",
-        "vss_numerics.h", "vss.h", "Makefile"]
+        "vss_returns.hip", "vss_scripted.hip", "vss_perceive.hip", "vss_actuate.hip", "vss_estimate.hip", "vss_track.hip",
+        "vss_setplay.hip", "vss_referee.hip", "vss_loss_row.h", "vss_numerics.h", "vss_placement.h", "vss.h", "Makefile"]
     assert N.HEADER in N.STAMPED and all(os.path.isfile(p) for p in N.STAMPED)
     hips = sorted(f for f in os.listdir(N.CSRC) if f.endswith(".hip"))
     assert hips == sorted(f for f in files if f.endswith(".hip"))  # no kernel source left out of the stamp

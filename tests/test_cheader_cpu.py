@@ -141,7 +141,7 @@ def test_the_loaded_library_carries_the_headers_types():
     """load() binds through bind(): every entry point of the loaded library has the parsed restype and argtypes, a
     pointer never an integer slot, and the modules' names are the header's values."""
     lib = N.load()
-    assert len(N.ABI.functions) == 63 and tuple(N.ABI.functions) == N.EXPORTED
+    assert len(N.ABI.functions) == 66 and tuple(N.ABI.functions) == N.EXPORTED
     for name, (restype, argtypes) in N.ABI.functions.items():
         fn = getattr(lib, name)
         assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
@@ -159,7 +159,12 @@ def test_the_loaded_library_carries_the_headers_types():
                "vss_mirror_io": N.VssMirrorIO, "vss_actor_groups": N.VssActorGroups,
                "vss_perceive_layout": N.VssPerceiveLayout, "vss_perceive_noise": N.VssPerceiveNoise,
                "vss_actuate_layout": N.VssActuateLayout, "vss_actuate_params": N.VssActuateParams,
-               "vss_estimate_layout": N.VssEstimateLayout}
+               "vss_estimate_layout": N.VssEstimateLayout,
+               "vss_track_layout": N.VssTrackLayout, "vss_track_params": N.VssTrackParams,
+               "vss_setplay_entity": N.VssSetplayEntity, "vss_setplay_play": N.VssSetplayPlay,
+               "vss_setplay_table": N.VssSetplayTable, "vss_setplay_view": N.VssSetplayView,
+               "vss_referee_play": N.VssRefereePlay, "vss_referee_table": N.VssRefereeTable,
+               "vss_referee_params": N.VssRefereeParams}
     assert structs == N.ABI.structs
 
 
@@ -183,7 +188,7 @@ def test_struct_layouts_equal_the_c_compilers(tmp_path):
     subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.dirname(N.HEADER), "-o", str(exe), str(src)],
                    check=True, capture_output=True, text=True)
     got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")[:-1]
-    assert len(N.ABI.structs) == 13 and got == want
+    assert len(N.ABI.structs) == 22 and got == want
 
 
 def test_the_oracles_mirrors_equal_the_derived_ones():

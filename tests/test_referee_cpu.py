@@ -1,5 +1,5 @@
-"""The referee without a GPU (include/vss_referee.h, vss_amd/referee.py): the unit's own header, library
-and source stamp beside the core's and the set plays', the entry's argument checks on addresses that are never
+"""The referee without a GPU (include/vss.h, vss_amd/referee.py): the unit's part of the one header, library
+and source stamp, the entry's argument checks on addresses that are never
 dereferenced, the parameter and table rules, the float32 specification `reference_referee` on hand-built states -- each
 counter at its threshold, the precedence, max_stops, a done field, the >= 0 sides, the other goal's area -- its placement
 tied to `reference_setplay` bit for bit, and the flags' plumbing."""
@@ -13,7 +13,7 @@ import shutil
 import numpy as np
 import pytest
 
-from test_setplay_cpu import exported, fresh, same_bits
+from test_setplay_cpu import exported, fresh, same_bits, stale_copy_is_refused
 from vss_amd import _native as N
 from vss_amd import checkpoint as CK
 from vss_amd import cheader
@@ -42,47 +42,40 @@ def call(n_fields=64, tab=None, prm=None, done=FAKE, done_stride=1, state=FAKE +
                                 7, 3, done, done_stride, state, dof, counters, nv, None if null_views else arr, counts, verdict)
 
 
-# ---- the unit: its own header, library and stamp ---------------------------------------------------------------------
+# ---- the referee's part of the one ABI and the one library -------------------------------------------------------------
 def test_the_header_parses_and_the_library_exports_exactly_its_functions():
-    with open(R.HEADER) as f:
+    with open(N.HEADER) as f:
         h = cheader.parse(f.read())
-    assert list(h.functions) == ["vss_referee_abi_version", "vss_referee_source_hash", "vss_referee"] == list(R.EXPORTED)
-    assert sorted(h.structs) == ["vss_referee_entity", "vss_referee_params", "vss_referee_play", "vss_referee_table",
-                                 "vss_referee_view"]
-    assert h.constants["VSS_REFEREE_ABI_VERSION"] == 1 and h.constants["VSS_REFEREE_CODES"] == 8 == R.CODES
+    assert [name for name in h.functions if "referee" in name] == ["vss_referee"] and "vss_referee" in N.EXPORTED
+    assert sorted(name for name in h.structs if "referee" in name) == ["vss_referee_params", "vss_referee_play", "vss_referee_table"]
+    assert {k: v for k, v in h.constants.items() if "REFEREE" in k} == {"VSS_REFEREE_PLAYS": 3, "VSS_REFEREE_CODES": 8}
+    assert R.CODES == 8 == N.REFEREE_CODES
+    assert (R.VssRefereePlay, R.VssRefereeTable, R.VssRefereeParams) == (N.VssRefereePlay, N.VssRefereeTable, N.VssRefereeParams)
+    assert R.VssRefereeView is S.VssSetplayView and R.VssRefereeEntity is S.VssSetplayEntity  # one struct each in the header
     assert ctypes.sizeof(R.VssRefereeEntity) == 20 and ctypes.sizeof(R.VssRefereePlay) == 152
     assert ctypes.sizeof(R.VssRefereeTable) == 456 and ctypes.sizeof(R.VssRefereeParams) == 24
     assert ctypes.sizeof(R.VssRefereeView) == 40
-    assert [n for n, _ in R.VssRefereeView._fields_] == [n for n, _ in S.VssSetplayView._fields_]
-    assert [n for n, _ in R.VssRefereeEntity._fields_] == [n for n, _ in S.VssSetplayEntity._fields_]
-    lib = R.load()
-    assert lib.vss_referee.argtypes == h.functions["vss_referee"][1] and lib.vss_referee_abi_version() == 1
-    assert os.path.basename(R.LIB_PATH) == "libvss_referee.so" and os.path.dirname(R.LIB_PATH) == os.path.dirname(N.LIB_PATH)
+    assert [ctypes.sizeof(h.structs["vss_referee_" + n]) for n in ("play", "table", "params")] == [152, 456, 24]
+    assert N.load().vss_referee.argtypes == h.functions["vss_referee"][1]
     if shutil.which("nm"):
-        assert exported(R.LIB_PATH, "vss_") == sorted(h.functions)
-        for other in (N.LIB_PATH, S.LIB_PATH):  # the core's and the set plays' inventories are as they were
-            assert not [s for s in exported(other, "vss_") if "referee" in s]
+        assert exported(N.LIB_PATH, "vss_referee") == ["vss_referee"]
+        assert exported(N.LIB_PATH, "vss_") == sorted(h.functions)
 
 
-def test_the_stamp_covers_the_units_sources_and_a_stale_library_is_refused():
-    names = [os.path.relpath(p, R.CSRC) for p in R.STAMPED]
-    assert names == ["vss_referee.hip", "../csrc/vss_numerics.h", "../../include/vss_referee.h", "Makefile"]
-    with open(os.path.join(R.CSRC, "Makefile")) as f:
-        text = f.read()
-    assert re.search(r"^STAMPED := vss_referee\.hip:STEP_FLAGS \.\./csrc/vss_numerics\.h \.\./\.\./include/vss_referee\.h Makefile$",
-                     text, re.M)
-    assert re.search(r"^STEP_FLAGS := \$\(COMMON\) -ffp-contract=off$", text, re.M)
-    assert re.search(r"^REFEREE_OUT \?= ", text, re.M) and re.search(r"^REFEREE_OBJ \?= ", text, re.M)
-    assert re.search(r"^resource-usage:", text, re.M)
-    lib = R.load()
-    fn = lib.vss_referee_source_hash
-    fn.restype = ctypes.c_char_p
-    assert fn().decode() == R.source_hash() and R.source_hash() not in (N.source_hash(), S.source_hash())
-    with pytest.raises(N.NativeError, match="built from other sources.*rebuild it with.*make -C"):
-        R.verify_source_hash(lib, expected="0" * 16)
-    with open(os.path.join(N.CSRC, "Makefile")) as f:
-        core = f.read()
-    assert "$(MAKE) -C ../csrc_referee\n" in core and "$(MAKE) -C ../csrc_referee clean" in core
+def test_the_unit_is_one_of_the_core_librarys_and_nothing_is_packaged_beside_it():
+    assert [os.path.basename(p) for p in N.STAMPED].count("vss_referee.hip") == 1
+    assert os.path.join(N.CSRC, "vss_referee.hip") in N.STAMPED and os.path.join(N.CSRC, "vss_placement.h") in N.STAMPED
+    assert [os.path.join(d, f) for d, _, files in os.walk(N.CSRC) for f in files if f == "Makefile" or f.endswith(".mk")] \
+        == [os.path.join(N.CSRC, "Makefile")]
+    for name in ("LIB_PATH", "STAMPED", "CSRC", "HEADER", "ABI", "EXPORTED", "ABI_VERSION", "source_hash", "verify_source_hash"):
+        assert not hasattr(R, name), name
+    assert R.load is N.load  # the module's own name for the one loader
+    assert not os.path.exists(os.path.join(os.path.dirname(N.HEADER), "vss_referee.h"))
+    assert [d for d in os.listdir(os.path.dirname(N.CSRC)) if d.startswith("csrc")] == ["csrc"]  # no unit beside the core
+
+
+def test_the_stamp_covers_the_units_sources_and_a_stale_library_is_refused(tmp_path, monkeypatch):
+    stale_copy_is_refused("vss_referee.hip", "STEP_FLAGS", tmp_path, monkeypatch)
 
 
 # ---- the entry's refusals ----------------------------------------------------------------------------------------------

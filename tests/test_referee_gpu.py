@@ -1,4 +1,4 @@
-"""vss_referee on the GPU (csrc_referee/vss_referee.hip): the kernel equals
+"""vss_referee on the GPU (csrc/vss_referee.hip): the kernel equals
 vss_amd.referee.reference_referee bit for bit -- state, dof velocities, rows, counters, verdict and counts -- for every
 view a wrapper uses and FULL, for a lone lane, a wave's tail, a wave that leaves early, a second workgroup and a tail
 behind three, with and without a done mask; writes nothing outside its buffers and nothing of a field it does not
@@ -318,7 +318,7 @@ def test_binding_refusals_and_a_state_dict_round_trip():
     for bad in (done[:-1], done.int(), done.cpu()):
         with pytest.raises(ValueError, match="done must be"):
             ref.call(env.state, dof, [(obs, R.view_sa())], bad)
-    with pytest.raises(N.NativeError, match="bad argument"):
+    with pytest.raises(N.NativeError, match="invalid argument"):
         ref.call(env.state, dof, [(torch.zeros((n + 8, 52), device=DEV), R.View(1, 0, 2, 1, 0))], done)
     with pytest.raises(N.NativeError, match="no CPU path"):
         R.Referee(n, R.RefTable(), ON, 9, "cpu")

@@ -1,5 +1,5 @@
-"""The set plays without a GPU (include/vss_setplay.h, vss_amd/setplay.py): the unit's own header,
-library and source stamp beside the core's, the entry's argument checks on addresses that are never dereferenced,
+"""The set plays without a GPU (include/vss.h, vss_amd/setplay.py): the unit's part of the one header,
+library and source stamp, the entry's argument checks on addresses that are never dereferenced,
 Table.validate rule by rule, the float32 specification `reference_setplay` on known answers -- no jitter, each flip
 alone, the share and the weights' statistics, the clearance of 10,000 draws per built-in -- and the flags' plumbing."""
 import argparse
@@ -53,27 +53,42 @@ def call(n_fields=64, tab=None, done=FAKE, done_stride=1, state=FAKE + GAP, view
                                 nv, None if null_views else arr, counts, chosen)
 
 
-# ---- the unit: its own header, library and stamp ---------------------------------------------------------------------
+# ---- the set plays' part of the one ABI and the one library -----------------------------------------------------------
 def exported(path, prefix):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return sorted(m.group(1) for m in re.finditer(rf"^\S+\s+T\s+({prefix}\w*)$", out, flags=re.M))
 
 
 def test_the_header_parses_and_the_library_exports_exactly_its_functions():
-    with open(S.HEADER) as f:
+    with open(N.HEADER) as f:
         h = cheader.parse(f.read())
-    assert list(h.functions) == ["vss_setplay_abi_version", "vss_setplay_source_hash", "vss_setplay"] == list(S.EXPORTED)
-    assert sorted(h.structs) == ["vss_setplay_entity", "vss_setplay_play", "vss_setplay_table", "vss_setplay_view"]
-    assert h.constants["VSS_SETPLAY_ABI_VERSION"] == 1 and h.constants["VSS_SETPLAY_MAX_PLAYS"] == 8 == S.MAX_PLAYS
+    assert [name for name in h.functions if "setplay" in name] == ["vss_setplay"] and "vss_setplay" in N.EXPORTED
+    assert sorted(name for name in h.structs if "setplay" in name) == ["vss_setplay_entity", "vss_setplay_play",
+                                                                       "vss_setplay_table", "vss_setplay_view"]
+    assert {k: v for k, v in h.constants.items() if "SETPLAY" in k} == {"VSS_SETPLAY_MAX_PLAYS": 8}
+    assert S.MAX_PLAYS == 8 == N.SETPLAY_MAX_PLAYS
+    assert (S.VssSetplayEntity, S.VssSetplayPlay, S.VssSetplayTable, S.VssSetplayView) \
+        == (N.VssSetplayEntity, N.VssSetplayPlay, N.VssSetplayTable, N.VssSetplayView)
     assert ctypes.sizeof(S.VssSetplayEntity) == 20 and ctypes.sizeof(S.VssSetplayPlay) == 7 * 20 + 24
     assert ctypes.sizeof(S.VssSetplayTable) == 12 + 8 * 164 and ctypes.sizeof(S.VssSetplayView) == 40
+    assert [ctypes.sizeof(h.structs["vss_setplay_" + n]) for n in ("entity", "play", "table", "view")] == [20, 164, 12 + 8 * 164, 40]
     assert [n for n, _ in S.VssSetplayView._fields_] == ["obs"] + [n for n, _ in N.VssPerceiveLayout._fields_]
-    lib = S.load()
-    assert lib.vss_setplay.argtypes == h.functions["vss_setplay"][1] and lib.vss_setplay_abi_version() == 1
-    assert os.path.basename(S.LIB_PATH) == "libvss_setplay.so" and os.path.dirname(S.LIB_PATH) == os.path.dirname(N.LIB_PATH)
+    assert N.load().vss_setplay.argtypes == h.functions["vss_setplay"][1]
     if shutil.which("nm"):
-        assert exported(S.LIB_PATH, "vss_") == sorted(h.functions)
-        assert not [s for s in exported(N.LIB_PATH, "vss_") if "setplay" in s]  # the core's inventory is as it was
+        assert exported(N.LIB_PATH, "vss_setplay") == ["vss_setplay"]
+        assert exported(N.LIB_PATH, "vss_") == sorted(h.functions)
+
+
+def test_the_unit_is_one_of_the_core_librarys_and_nothing_is_packaged_beside_it():
+    assert [os.path.basename(p) for p in N.STAMPED].count("vss_setplay.hip") == 1
+    assert os.path.join(N.CSRC, "vss_setplay.hip") in N.STAMPED and os.path.join(N.CSRC, "vss_placement.h") in N.STAMPED
+    assert [os.path.join(d, f) for d, _, files in os.walk(N.CSRC) for f in files if f == "Makefile" or f.endswith(".mk")] \
+        == [os.path.join(N.CSRC, "Makefile")]
+    for name in ("LIB_PATH", "STAMPED", "CSRC", "HEADER", "ABI", "EXPORTED", "ABI_VERSION", "source_hash", "verify_source_hash"):
+        assert not hasattr(S, name), name
+    assert S.load is N.load  # the module's own name for the one loader
+    assert not os.path.exists(os.path.join(os.path.dirname(N.HEADER), "vss_setplay.h"))
+    assert [d for d in os.listdir(os.path.dirname(N.CSRC)) if d.startswith("csrc")] == ["csrc"]  # no unit beside the core
 
 
 def test_the_parser_takes_a_member_of_an_earlier_struct_and_nothing_more():
@@ -91,20 +106,39 @@ def test_the_parser_takes_a_member_of_an_earlier_struct_and_nothing_more():
             cheader.parse(text)
 
 
-def test_the_stamp_covers_the_units_sources_and_a_stale_library_is_refused():
-    names = [os.path.relpath(p, S.CSRC) for p in S.STAMPED]
-    assert names == ["vss_setplay.hip", "../csrc/vss_numerics.h", "../../include/vss_setplay.h", "Makefile"]
-    lib = S.load()
-    fn = lib.vss_setplay_source_hash
-    fn.restype = ctypes.c_char_p
-    assert fn().decode() == S.source_hash() and S.source_hash() != N.source_hash()
-    with pytest.raises(N.NativeError, match="built from other sources.*rebuild it with.*make -C"):
-        S.verify_source_hash(lib, expected="0" * 16)
+def stale_copy_is_refused(name, flags, tmp_path, monkeypatch):
+    """A library built before csrc/<name> was edited is refused at load, and the hash a state file records
+    (checkpoint.source_hash is N.source_hash) changes with that edit.  `flags`: the word's flag set on the STAMPED line."""
     with open(os.path.join(N.CSRC, "Makefile")) as f:
-        core = f.read()
-    assert "$(MAKE) -C ../csrc_setplay\n" in core and "$(MAKE) -C ../csrc_setplay clean" in core
-    with open(os.path.join(S.CSRC, "Makefile")) as f:
-        assert re.search(r"^STEP_FLAGS := \$\(COMMON\) -ffp-contract=off$", f.read(), re.M)
+        text = f.read()
+    (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", text, flags=re.M)
+    assert (name + ":" + flags if flags else name) in line.split()
+    assert re.search(r"^STEP_FLAGS := \$\(COMMON\) -ffp-contract=off$", text, re.M) and re.search(r"^resource-usage:", text, re.M)
+    at = list(N.STAMPED).index(os.path.join(N.CSRC, name))
+    assert all(os.path.isfile(p) for p in N.STAMPED)
+    lib = N.load()
+    N.verify_source_hash(lib)
+    with pytest.raises(N.NativeError, match="built from other sources"):
+        N.verify_source_hash(lib, expected="0" * 16)
+    before = N.source_hash()
+    assert CK.source_hash() == before
+    src = os.path.join(tmp_path, name)
+    shutil.copy(N.STAMPED[at], src)
+    with open(src, "a") as f:
+        f.write("// edited after the build\n")
+    monkeypatch.setattr(N, "STAMPED", tuple(N.STAMPED[:at]) + (src,) + tuple(N.STAMPED[at + 1:]))
+    monkeypatch.setattr(N, "_lib", None)
+    with pytest.raises(N.NativeError, match=r"built from other sources.*rebuild it with.*make -C"):
+        N.load()
+    assert N.source_hash() != before and CK.source_hash() == N.source_hash()
+
+
+def test_the_stamp_covers_the_units_sources_and_a_stale_library_is_refused(tmp_path, monkeypatch):
+    stale_copy_is_refused("vss_setplay.hip", "STEP_FLAGS", tmp_path, monkeypatch)
+
+
+def test_the_stamp_covers_the_shared_placement_header(tmp_path, monkeypatch):
+    stale_copy_is_refused("vss_placement.h", "", tmp_path, monkeypatch)
 
 
 # ---- the entry's refusals ----------------------------------------------------------------------------------------------

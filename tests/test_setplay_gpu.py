@@ -1,4 +1,4 @@
-"""vss_setplay on the GPU (csrc_setplay/vss_setplay.hip): the kernel equals
+"""vss_setplay on the GPU (csrc/vss_setplay.hip): the kernel equals
 vss_amd.setplay.reference_setplay bit for bit -- state, rows, chosen and counts after every one of 6 calls, for every
 view a wrapper uses and FULL, for done masks that are empty, full, one lane per wave and a lone last field, tables of 1
 and 8 plays, shares 0, 0.5 and 1 and `only=` -- writes nothing outside its buffers, its rows are what
@@ -271,7 +271,7 @@ def test_binding_refusals_and_a_state_dict_round_trip():
     for bad in (done[:-1], done.int(), done.cpu(), None):
         with pytest.raises(ValueError, match="done must be"):
             st.stage(env.state, [(obs, S.view_sa())], bad)
-    with pytest.raises(N.NativeError, match="bad argument"):
+    with pytest.raises(N.NativeError, match="invalid argument"):
         st.stage(env.state, [(torch.zeros((n + 8, 52), device=DEV), S.View(1, 0, 2, 1, 0))], done)
     with pytest.raises(ValueError, match="only=9"):
         st.start(env.state, (), only=9)

@@ -1,5 +1,5 @@
-"""The tracking channel without a GPU (include/vss_track.h, vss_amd/track.py): the unit's own header,
-library and source stamp beside the core's, the entry's argument checks on addresses that are never dereferenced, the
+"""The tracking channel without a GPU (include/vss.h, vss_amd/track.py): the unit's part of the one header,
+library and source stamp, the entry's argument checks on addresses that are never dereferenced, the
 flags' plumbing, and the float32 specification `reference_track` on known answers -- bitwise copies, gain 1, each
 gate at its threshold, the episode edges, one world -- and against the project's own physics (the C oracle) on
 contact-free scenes: without noise the filter stays on the measurement, with noise it is closer to the truth."""
@@ -57,52 +57,64 @@ def run(obs, term, dones, delay, params):
     return out
 
 
-# ---- the unit: its own header, library and stamp ---------------------------------------------------------------------
+# ---- the channel's part of the one ABI and the one library -------------------------------------------------------------
 def exported(path, prefix):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return sorted(m.group(1) for m in re.finditer(rf"^\S+\s+T\s+({prefix}\w*)$", out, flags=re.M))
 
 
 def test_the_header_parses_and_the_library_exports_exactly_its_functions():
-    with open(T.HEADER) as f:
+    with open(N.HEADER) as f:
         h = cheader.parse(f.read())
-    assert list(h.functions) == ["vss_track_abi_version", "vss_track_source_hash", "vss_track"] == list(T.EXPORTED)
-    assert sorted(h.structs) == ["vss_track_layout", "vss_track_params"]
-    assert h.constants["VSS_TRACK_ABI_VERSION"] == 1 and h.constants["VSS_TRACK_MAX_DELAY"] == 15 == T.MAX_DELAY
+    assert [name for name in h.functions if "track" in name] == ["vss_track"] and "vss_track" in N.EXPORTED
+    assert sorted(name for name in h.structs if "track" in name) == ["vss_track_layout", "vss_track_params"]
+    assert {k: v for k, v in h.constants.items() if "TRACK" in k} == {"VSS_TRACK_MAX_DELAY": 15}
+    assert T.MAX_DELAY == 15 == N.TRACK_MAX_DELAY
+    assert T.VssTrackLayout is N.VssTrackLayout and T.VssTrackParams is N.VssTrackParams
     assert ctypes.sizeof(T.VssTrackLayout) == 24 == ctypes.sizeof(N.VssEstimateLayout) and ctypes.sizeof(T.VssTrackParams) == 20
+    assert ctypes.sizeof(h.structs["vss_track_layout"]) == 24 and ctypes.sizeof(h.structs["vss_track_params"]) == 20
     assert [n for n, _ in T.VssTrackLayout._fields_] == [n for n, _ in N.VssEstimateLayout._fields_]
-    lib = T.load()
-    assert lib.vss_track.argtypes == h.functions["vss_track"][1] and lib.vss_track_abi_version() == 1
-    assert os.path.basename(T.LIB_PATH) == "libvss_track.so" and os.path.dirname(T.LIB_PATH) == os.path.dirname(N.LIB_PATH)
+    assert N.load().vss_track.argtypes == h.functions["vss_track"][1]
     if shutil.which("nm"):
-        assert exported(T.LIB_PATH, "vss_") == sorted(h.functions)
-        assert not [s for s in exported(N.LIB_PATH, "vss_") if "track" in s]  # the core's inventory is as it was
+        assert exported(N.LIB_PATH, "vss_track") == ["vss_track"]
+        assert exported(N.LIB_PATH, "vss_") == sorted(h.functions)
+
+
+def test_the_unit_is_one_of_the_core_librarys_and_nothing_is_packaged_beside_it():
+    assert [os.path.basename(p) for p in N.STAMPED].count("vss_track.hip") == 1
+    assert os.path.join(N.CSRC, "vss_track.hip") in N.STAMPED
+    assert [os.path.join(d, f) for d, _, files in os.walk(N.CSRC) for f in files if f == "Makefile" or f.endswith(".mk")] \
+        == [os.path.join(N.CSRC, "Makefile")]
+    for name in ("LIB_PATH", "STAMPED", "CSRC", "HEADER", "ABI", "EXPORTED", "ABI_VERSION", "source_hash", "verify_source_hash"):
+        assert not hasattr(T, name), name
+    assert T.load is N.load  # the module's own name for the one loader
+    assert not os.path.exists(os.path.join(os.path.dirname(N.HEADER), "vss_track.h"))
+    assert [d for d in os.listdir(os.path.dirname(N.CSRC)) if d.startswith("csrc")] == ["csrc"]  # no unit beside the core
 
 
 def test_the_stamp_covers_the_units_list_and_a_stale_library_is_refused_at_load(tmp_path, monkeypatch):
-    with open(os.path.join(T.CSRC, "Makefile")) as f:
+    """A library built before vss_track.hip was edited is refused, and the hash a state file records
+    (checkpoint.source_hash is N.source_hash) changes with that edit."""
+    with open(os.path.join(N.CSRC, "Makefile")) as f:
         (line,) = re.findall(r"^STAMPED\s*:=\s*(.*)$", f.read(), flags=re.M)
-    assert line.split() == ["vss_track.hip:STEP_FLAGS", "../csrc/vss_numerics.h", "../../include/vss_track.h", "Makefile"]
-    assert T.STAMPED == (os.path.join(T.CSRC, "vss_track.hip"), os.path.join(N.CSRC, "vss_numerics.h"), T.HEADER,
-                         os.path.join(T.CSRC, "Makefile"))
-    assert os.path.dirname(T.CSRC) == os.path.dirname(N.CSRC) and T.CSRC != N.CSRC  # a sibling of csrc/, not under it
-    lib = T.load()
-    T.verify_source_hash(lib)
+    assert "vss_track.hip:STEP_FLAGS" in line.split()
+    at = list(N.STAMPED).index(os.path.join(N.CSRC, "vss_track.hip"))
+    assert all(os.path.isfile(p) for p in N.STAMPED)
+    lib = N.load()
+    N.verify_source_hash(lib)
     with pytest.raises(N.NativeError, match="built from other sources"):
-        T.verify_source_hash(lib, expected="0" * 16)
-    before = T.source_hash()
-    for at in (0, 1):  # an edit to vss_track.hip, an edit to the core's vss_numerics.h
-        src = os.path.join(tmp_path, os.path.basename(T.STAMPED[at]))
-        shutil.copy(T.STAMPED[at], src)
-        with open(src, "a") as f:
-            f.write("// edited after the build\n")
-        with monkeypatch.context() as m:
-            m.setattr(T, "STAMPED", tuple(T.STAMPED[:at]) + (src,) + tuple(T.STAMPED[at + 1:]))
-            m.setattr(T, "_lib", None)
-            with pytest.raises(N.NativeError, match=r"built from other sources.*make -C"):
-                T.load()
-            assert T.source_hash() != before
-    assert T.source_hash() == before and T.load() is lib
+        N.verify_source_hash(lib, expected="0" * 16)
+    before = N.source_hash()
+    assert CK.source_hash() == before
+    src = os.path.join(tmp_path, "vss_track.hip")
+    shutil.copy(N.STAMPED[at], src)
+    with open(src, "a") as f:
+        f.write("// edited after the build\n")
+    monkeypatch.setattr(N, "STAMPED", tuple(N.STAMPED[:at]) + (src,) + tuple(N.STAMPED[at + 1:]))
+    monkeypatch.setattr(N, "_lib", None)
+    with pytest.raises(N.NativeError, match=r"built from other sources.*make -C"):
+        N.load()
+    assert N.source_hash() != before and CK.source_hash() == N.source_hash()
 
 
 # ---- the entry's refusals ----------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""vss_track on the GPU (csrc_track/vss_track.hip): the kernel equals vss_amd.track.reference_track bit
+"""vss_track on the GPU (csrc/vss_track.hip): the kernel equals vss_amd.track.reference_track bit
 for bit -- both outputs, the filtered rows, the command ring and the ages after every one of 12 calls, for every layout
 a wrapper uses, delays 0, 1, 3, 15, with a kind off, with the gates off, on rows that follow the filter and rows that
 jump through each gate -- writes nothing outside its rows, and the Tracked wrapper's closed loop on perceived envs

@@ -1,9 +1,9 @@
-/* Host-side argument validation of vss_referee (include/vss_referee.h) as a stand-alone program for ASan + UBSan.
- * Every call below is rejected (or returns VSS_REFEREE_OK for a zero size) before any HIP call, so it runs on a
+/* Host-side argument validation of vss_referee (include/vss.h) as a stand-alone program for ASan + UBSan.
+ * Every call below is rejected (or returns VSS_OK for a zero size) before any HIP call, so it runs on a
  * CPU-only machine; the pointers are fake, non-null and never dereferenced.  Build the host code of
  * vss_referee.hip with the sanitizers and run (from the repository root):
  *
- *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc_referee
+ *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc
  *   SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
  *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off $SAN -c $C/vss_referee.hip -o $O/rf.o
  *   hipcc -fsanitize=address,undefined -fno-sanitize-recover=undefined -g -x c tools/referee_args_check.c \
@@ -13,7 +13,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../include/vss_referee.h"
+#include "../include/vss.h"
 
 static int failures = 0;
 #define EXPECT(call, want)                                                        \
@@ -28,8 +28,8 @@ static int failures = 0;
 #define FAKE ((uintptr_t)1 << 20)
 #define GAP ((uintptr_t)1 << 24) /* between two fake buffers: further than any extent of 64 fields */
 #define ROW ((uintptr_t)208)
-#define E_ARG VSS_REFEREE_E_ARG
-#define OK VSS_REFEREE_OK
+#define E_ARG VSS_E_ARG
+#define OK VSS_OK
 
 typedef struct call_args {
   int64_t n;
@@ -38,18 +38,18 @@ typedef struct call_args {
   uintptr_t done, state, dof, counters, counts, verdict;
   int64_t done_stride;
   int32_t n_views;
-  vss_referee_view view[2];
+  vss_setplay_view view[2];
   int null_tab, null_prm, null_views;
 } call_args;
 
 /* the free ball, the penalty and the goal kick as blue's own piece in the +y half */
-static const vss_referee_entity FREE_BALL[7] = {{.375f, .4f, 0, 0, 0}, {.175f, .4f, 0, .01f, .2f}, {-.10f, 0, 0, .03f, .5f},
+static const vss_setplay_entity FREE_BALL[7] = {{.375f, .4f, 0, 0, 0}, {.175f, .4f, 0, .01f, .2f}, {-.10f, 0, 0, .03f, .5f},
     {-.62f, .05f, 0, .02f, .5f}, {.575f, .4f, 3.1415927f, .01f, .2f}, {.45f, -.10f, 3.1415927f, .03f, .5f},
     {.66f, .05f, 3.1415927f, .02f, .5f}};
-static const vss_referee_entity PENALTY[7] = {{.375f, 0, 0, 0, 0}, {.28f, 0, 0, .01f, .3f}, {-.10f, .30f, 0, .03f, .5f},
+static const vss_setplay_entity PENALTY[7] = {{.375f, 0, 0, 0, 0}, {.28f, 0, 0, .01f, .3f}, {-.10f, .30f, 0, .03f, .5f},
     {-.10f, -.30f, 0, .03f, .5f}, {-.15f, .10f, 3.1415927f, .02f, .5f}, {-.15f, -.10f, 3.1415927f, .02f, .5f},
     {.68f, 0, 1.5707964f, .02f, .3f}};
-static const vss_referee_entity GOAL_KICK[7] = {{-.60f, .10f, 0, 0, 0}, {-.30f, .30f, 0, .03f, .5f}, {-.30f, -.30f, 0, .03f, .5f},
+static const vss_setplay_entity GOAL_KICK[7] = {{-.60f, .10f, 0, 0, 0}, {-.30f, .30f, 0, .03f, .5f}, {-.30f, -.30f, 0, .03f, .5f},
     {-.69f, .10f, 0, 0, .2f}, {0, 0, 3.1415927f, .03f, .5f}, {.20f, .30f, 3.1415927f, .03f, .5f},
     {.66f, 0, 3.1415927f, .02f, .5f}};
 
@@ -76,7 +76,6 @@ static int run(call_args a) {
 
 int main(void) {
   call_args a;
-  EXPECT(vss_referee_abi_version(), VSS_REFEREE_ABI_VERSION);
   /* zero size: OK, no launch -- with a done mask and without, no views, no counts or verdict, FULL, a mirror, every call off */
   a = good(); a.n = 0; EXPECT(run(a), OK);
   a = good(); a.n = 0; a.done = 0; a.done_stride = 0; EXPECT(run(a), OK);

@@ -1,9 +1,9 @@
-/* Host-side argument validation of vss_setplay (include/vss_setplay.h) as a stand-alone program for ASan + UBSan.
- * Every call below is rejected (or returns VSS_SETPLAY_OK for a zero size) before any HIP call, so it runs on a
+/* Host-side argument validation of vss_setplay (include/vss.h) as a stand-alone program for ASan + UBSan.
+ * Every call below is rejected (or returns VSS_OK for a zero size) before any HIP call, so it runs on a
  * CPU-only machine; the pointers are fake, non-null and never dereferenced.  Build the host code of
  * vss_setplay.hip with the sanitizers and run (from the repository root):
  *
- *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc_setplay
+ *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc
  *   SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
  *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off $SAN -c $C/vss_setplay.hip -o $O/sp.o
  *   hipcc -fsanitize=address,undefined -fno-sanitize-recover=undefined -g -x c tools/setplay_args_check.c \
@@ -13,7 +13,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../include/vss_setplay.h"
+#include "../include/vss.h"
 
 static int failures = 0;
 #define EXPECT(call, want)                                                        \
@@ -28,8 +28,8 @@ static int failures = 0;
 #define FAKE ((uintptr_t)1 << 20)
 #define GAP ((uintptr_t)1 << 24) /* between two fake buffers: further than any extent of 64 fields */
 #define ROW ((uintptr_t)208)
-#define E_ARG VSS_SETPLAY_E_ARG
-#define OK VSS_SETPLAY_OK
+#define E_ARG VSS_E_ARG
+#define OK VSS_OK
 
 typedef struct call_args {
   int64_t n;
@@ -71,7 +71,6 @@ static int run(call_args a) {
 
 int main(void) {
   call_args a;
-  EXPECT(vss_setplay_abi_version(), VSS_SETPLAY_ABI_VERSION);
   /* zero size: OK, no launch -- a step call, a start call, no views, no counts or chosen, FULL, a mirror, 8 plays */
   a = good(); a.n = 0; EXPECT(run(a), OK);
   a = good(); a.n = 0; a.done = 0; a.done_stride = 0; EXPECT(run(a), OK);

@@ -1,9 +1,9 @@
-/* Host-side argument validation of vss_track (include/vss_track.h) as a stand-alone program for ASan + UBSan.
- * Every call below is rejected (or returns VSS_TRACK_OK for a zero size) before any HIP call, so it runs on a
+/* Host-side argument validation of vss_track (include/vss.h) as a stand-alone program for ASan + UBSan.
+ * Every call below is rejected (or returns VSS_OK for a zero size) before any HIP call, so it runs on a
  * CPU-only machine; the pointers are fake, non-null and never dereferenced.  Build the host code of
  * vss_track.hip with the sanitizers and run (from the repository root):
  *
- *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc_track
+ *   O=tools/_build; mkdir -p $O; C=rsoccer-isaac-cleanrl_amd/csrc
  *   SAN="-Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined"
  *   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off $SAN -c $C/vss_track.hip -o $O/tr.o
  *   hipcc -fsanitize=address,undefined -fno-sanitize-recover=undefined -g -x c tools/track_args_check.c \
@@ -13,7 +13,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "../include/vss_track.h"
+#include "../include/vss.h"
 
 static int failures = 0;
 #define EXPECT(call, want)                                                        \
@@ -28,8 +28,8 @@ static int failures = 0;
 #define FAKE ((uintptr_t)1 << 20)
 #define GAP ((uintptr_t)1 << 24) /* between two fake buffers: further than any extent of 64 fields */
 #define ROW ((uintptr_t)208)
-#define E_ARG VSS_TRACK_E_ARG
-#define OK VSS_TRACK_OK
+#define E_ARG VSS_E_ARG
+#define OK VSS_OK
 
 typedef struct call_args {
   int64_t n;
@@ -55,7 +55,6 @@ static int run(call_args a) {
 
 int main(void) {
   call_args a;
-  EXPECT(vss_track_abi_version(), VSS_TRACK_ABI_VERSION);
   /* zero size: OK, no launch -- a step call, a start call, two teams, no delay and no ring, the longest delay */
   a = good(); a.n = 0; EXPECT(run(a), OK);
   a = good(); a.n = 0; a.term = 0; a.term_out = 0; EXPECT(run(a), OK);
