@@ -54,6 +54,14 @@ def _ops(rows, k, n, seed):
     return x, w, b, gz, y_lo
 
 
+def _assert_multi_item(rows, k, n):
+    """From the library's own plan: the forward / backward of `rows` x n has more row tiles (128 rows where
+    n % 256 == 0, else 256) than blocks per feature tile, so some block runs several work items."""
+    blocks = N.load().vss_linear_tanh_backward_chunks_bf16x6(rows, k, n)
+    tiles = rows // (128 if n % 256 == 0 else 256)
+    assert 0 < blocks < tiles, (rows, k, n, blocks, tiles)
+
+
 SHAPES = [(256, 512), (512, 512), (512, 256), (64, 128), (128, 256)]   # (k, n) forward
 BSHAPES = [(256, 512), (512, 512), (512, 256), (128, 256), (256, 128)]  # backward: from n into k
 
@@ -224,12 +232,16 @@ def test_x6_persistent_multi_item_cfga_gpu(n):
     """Widths that are not multiples of 256 take the 128-feature x 256-row block (CfgA); at 131,072 rows
     every block runs several work items (n = 128: 512 items on 256 blocks; n = 384: 1,536 items on
     240 blocks with a fixed i tile per block), so the bias and column-sum bookkeeping of one i tile
-    per block is exercised across items.  Forward, backward and the column sums vs fp64."""
+    per block is exercised across items.  Forward, backward and the column sums vs fp64, each under the
+    single-item tests' bar: the L2 error at most 1.25 x hipBLASLt's fp32 result's (the error depends on k,
+    not on the row count)."""
     rows, k = 131072, 256
+    _assert_multi_item(rows, k, n)
     x, w, b, _, _ = _ops(rows, k, n, n)
     ref = torch.tanh(x.double() @ w.double().t() + b.double())
     e6 = _rel(linear_tanh_x6(x, w, b), ref)
-    assert e6[0] < 4e-6, e6
+    et = _rel(torch.addmm(b, x, w.t()).tanh_(), ref)
+    assert e6[0] < 4e-6 and e6[1] < 1.25 * et[1] + 1e-8, (e6, et)
     # backward from this n-wide layer into a k-wide tanh layer: P = W^T (k, n) -> n_out = k = 256 (CfgB)
     # and from a k-wide layer into the n-wide one: n_out = n (CfgA, multi-item)
     g = torch.Generator(device="cuda").manual_seed(n + 1)
@@ -349,12 +361,20 @@ def test_x6_refusals_gpu():
 def test_mixed_rows_match_fp64_gpu(rows):
     """Row counts that are not tile multiples (the reference's default minibatch: 4,095 envs x 128 / 4
     = 131,040 rows): the whole tiles on the x6 kernels, the ragged rest on hipBLASLt (below one tile:
-    the fp32-MFMA kernels), one result within the fp32 tolerances of the single-kernel tests."""
+    the fp32-MFMA kernels), one result within the fp32 tolerances of the single-kernel tests.  The whole
+    tiles' forward, backward and weight gradient also meet the single-item tests' L2 bar (at most 1.25 x
+    hipBLASLt's fp32 error on the same rows); at 131,040 rows their blocks run several work items."""
     x, w, b, gz, y_lo = _ops(rows, 512, 256, rows)
     ref = torch.tanh(x.double() @ w.double().t() + b.double())
     y = linear_tanh_mixed(x, w, b)
     assert _rel(y, ref)[0] < 4e-6
     main = rows // 256 * 256
+    if rows == 131040:
+        _assert_multi_item(main, 512, 256)
+        _assert_multi_item(main, 256, 512)
+    if main:
+        e6, et = _rel(y[:main], ref[:main]), _rel(torch.addmm(b, x[:main], w.t()).tanh_(), ref[:main])
+        assert e6[1] < 1.25 * et[1] + 1e-8, (e6, et)
     if 0 < main < rows:  # the ragged tail: hipBLASLt addmm + tanh, as torch computes it
         torch.testing.assert_close(y[main:], torch.addmm(b, x[main:], w.t()).tanh_(), rtol=0, atol=0)
     wo = torch.randn(6, 256, device="cuda") / 16
@@ -369,9 +389,17 @@ def test_mixed_rows_match_fp64_gpu(rows):
     refb = (g256.double() @ w2.double()) * (1 - y512.double() ** 2)
     gzm, dbm = linear_tanh_backward_mixed(g256, w2, y512)
     assert _rel(gzm, refb)[0] < 4e-6
+    if main:
+        et = _rel(g256[:main].mm(w2) * (1 - y512[:main] * y512[:main]), refb[:main])
+        e6 = _rel(gzm[:main], refb[:main])
+        assert e6[1] < 1.25 * et[1] + 1e-8, (e6, et)
     torch.testing.assert_close(dbm.double(), refb.sum(0), rtol=1e-5, atol=1e-5 * float(refb.sum(0).abs().max()))
     refw = g256.double().t() @ x.double()
     assert _rel(weight_grad_mixed(g256, x), refw)[0] < 4e-6
+    m64 = rows // 64 * 64  # the weight gradient's whole tiles
+    refm = g256[:m64].double().t() @ x[:m64].double()
+    e6, et = _rel(weight_grad_mixed(g256[:m64], x[:m64]), refm), _rel(g256[:m64].t().mm(x[:m64]), refm)
+    assert e6[1] < 1.25 * et[1] + 1e-8, (e6, et)
 
 
 @pytest.mark.gpu
