@@ -134,8 +134,28 @@ constexpr int kTabWords = 2 * 78;
 // waiting for a table load issued between the stream's stores drains every store before it
 // (measured in the ISA: an s_waitcnt vmcnt(0) per unrolled stream iteration).  ds_read waits
 // on lgkmcnt instead, which the stores do not touch.
-__device__ __forceinline__ void stage_obs_table(uint32_t* tab, int lane) {
-  for (int i = lane; i < kTabWords; i += kWave) tab[i] = kObsTab.w[i];
+// The copy has two halves.  load_obs_table issues the lane's three words (lane + 64 j) into
+// registers, unrolled and with no wait, so a kernel issues them together with its other inputs: one
+// round trip for all of them instead of a load -> wait -> ds_write loop in front of everything else.
+// stage_obs_table writes them to LDS where the kernel waits for its first inputs anyway.  Neither
+// half is predicated: the LDS copy is padded to three words per lane (kTabLds; the lanes past the
+// table's end read its last word again and write it into the padding), because the compiler sinks
+// a load whose only use is predicated down to that use, wait and all.  The table's LDS words lie
+// past the record block, so only the barrier that already precedes the first coop_store_obs orders
+// the two.
+constexpr int kTabPerLane = (kTabWords + kWave - 1) / kWave;
+constexpr int kTabLds = kTabPerLane * kWave;
+__device__ __forceinline__ void load_obs_table(int lane, uint32_t w[kTabPerLane]) {
+#pragma unroll
+  for (int j = 0; j < kTabPerLane; ++j) {
+    const int i = lane + j * kWave;
+    w[j] = kObsTab.w[i < kTabWords ? i : kTabWords - 1];
+  }
+}
+
+__device__ __forceinline__ void stage_obs_table(uint32_t* tab, int lane, const uint32_t w[kTabPerLane]) {
+#pragma unroll
+  for (int j = 0; j < kTabPerLane; ++j) tab[lane + j * kWave] = w[j];
 }
 
 // ---- math (transcendental-free; identical op sequence in oracle/vss_oracle.c) ----------------
@@ -362,6 +382,11 @@ __device__ __forceinline__ void physics_split(Bodies& b, const float a[12]) {
 // loads are outstanding; the compiler's waitcnt pass sees the builtin and drops later waits.
 __device__ __forceinline__ void wait_loads() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
+// Placed behind a kernel's last input load: the instruction scheduler moves nothing across it (it
+// emits no instruction).  Without it the first use of an early load, and the wait in front of that
+// use, is lifted in between the loads, and the loads behind it are issued a wait later.
+__device__ __forceinline__ void loads_issued() { __builtin_amdgcn_sched_barrier(0); }
+
 // ---- state I/O -----------------------------------------------------------------------------------
 // Addressing: a wave's accesses are a wave-uniform base (field f0 of a channel: ch * n + f0, in SGPRs)
 // plus the lane's 32-bit byte offset, so they compile to `global_load/store v, v_off, s[base]`.
@@ -412,28 +437,9 @@ __device__ __forceinline__ void store_bodies(float* __restrict__ st, int64_t n, 
 }
 
 // ---- wave-cooperative AoS <-> per-lane transposes through LDS -----------------------------------
-// A wave owns fields [f0, f0 + nv); their W-float records are contiguous in global memory.
-template <int W>
-__device__ __forceinline__ void coop_load(const float* __restrict__ g, int nv, float* lds, int lane) {
-  const int total = nv * W;
-  if constexpr (W % 4 == 0) {
-    const float4* g4 = reinterpret_cast<const float4*>(g);
-    for (int q = lane; q < total / 4; q += kWave) {
-      float4 v = at(g4, 16u * (uint32_t)q);
-      int e = q * 4, fl = e / W, k = e - fl * W;
-      float* d = lds + fl * kRec + k;
-      d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-  } else {
-    const float2* g2 = reinterpret_cast<const float2*>(g);
-    for (int q = lane; q < total / 2; q += kWave) {
-      float2 v = at(g2, 8u * (uint32_t)q);
-      int e = q * 2, fl = e / W, k = e - fl * W;
-      float* d = lds + fl * kRec + k;
-      d[0] = v.x; d[1] = v.y;
-    }
-  }
-}
+// A wave owns fields [f0, f0 + nv); their W-float records are contiguous in global memory.  Inwards
+// the rows are prefetched into registers and staged later (prefetch12 / stage12, prefetch_lrn /
+// stage_lrn below), so that their loads are issued with the wave's other inputs.
 
 // ---- wave-cooperative 16-B stores with a cache policy ---------------------------------------------
 // The streams go out through a buffer resource over exactly the wave's output block (base and size
@@ -803,18 +809,26 @@ __device__ __forceinline__ int64_t rewards_and_done(const vss_params& p, const B
   return (is_goal || progress >= (int64_t)p.max_episode_length) ? 1 : 0;
 }
 
+// The rows come in unpredicated: a lane whose piece lies past the wave's block loads the block's last
+// piece again (an address the wave reads anyway) and never stages it.  A predicated load is a branch
+// around the load, and behind a branch the compiler's wait for an earlier load has to assume that
+// the later ones were skipped: it then waits for all of them (vmcnt(0)) instead of the early ones.
+// NF: the fields a wave of the kernel holds at most (kFpw: two pieces per lane, kWave: three).
+template <int NF>
 __device__ __forceinline__ void prefetch12(const float* __restrict__ g, int nv, int lane, float4 pre[3]) {
   const float4* g4 = reinterpret_cast<const float4*>(g);
+  const int last = nv * 3 - 1;
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
+  for (int j = 0; j < (NF * 3 + kWave - 1) / kWave; ++j) {
     const int q = lane + j * kWave;
-    if (q < nv * 3) pre[j] = at(g4, 16u * (uint32_t)q);
+    pre[j] = at(g4, 16u * (uint32_t)(q < last ? q : last));
   }
 }
 
+template <int NF>
 __device__ __forceinline__ void stage12(const float4 pre[3], int nv, float* lds, int lane) {
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
+  for (int j = 0; j < (NF * 3 + kWave - 1) / kWave; ++j) {
     const int q = lane + j * kWave;
     if (q < nv * 3) {
       const int fl = q / 3, k = (q - fl * 3) * 4;
@@ -825,21 +839,23 @@ __device__ __forceinline__ void stage12(const float4 pre[3], int nv, float* lds,
 }
 
 // The learner action rows (nv, NL) of a wrapped-mode batch as float2 pieces (8-B aligned per the
-// ABI), prefetched into registers and later staged into the LDS record layout like stage12.
+// ABI), prefetched into registers and later staged into the LDS record layout like stage12; kFpw
+// fields at most, so one piece per lane for NL = 2 and two for NL = 6.
 template <int NL>
 __device__ __forceinline__ void prefetch_lrn(const float* __restrict__ g, int nv, int lane, float2 pre[2]) {
   const float2* g2 = reinterpret_cast<const float2*>(g);
+  const int last = nv * NL / 2 - 1;
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
+  for (int j = 0; j < (kFpw * NL / 2 + kWave - 1) / kWave; ++j) {
     const int q = lane + j * kWave;
-    if (q < nv * NL / 2) pre[j] = at(g2, 8u * (uint32_t)q);
+    pre[j] = at(g2, 8u * (uint32_t)(q < last ? q : last));
   }
 }
 
 template <int NL>
 __device__ __forceinline__ void stage_lrn(const float2 pre[2], int nv, float* lds, int lane) {
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
+  for (int j = 0; j < (kFpw * NL / 2 + kWave - 1) / kWave; ++j) {
     const int q = lane + j * kWave;
     if (q < nv * NL / 2) {
       const int e = q * 2, fl = e / NL, k = e - fl * NL;
@@ -952,21 +968,28 @@ struct StepArgs {
   uint32_t store_policy;  // cache policy of each store group (policy_word), set by launch_step
 };
 
+// The rows are issued first, the state behind them: the rows are what the kernel consumes first (the
+// LDS transpose), loads return in order, and so the wait before the transpose covers the rows (and
+// the gather table in front of them) while the 49 state and bookkeeping loads are still in flight.
 template <int MODE>
-__device__ __forceinline__ void load_batch(const StepArgs& args, int64_t f0, int nv, int fl, int lane, BatchIn& in) {
+__device__ __forceinline__ void load_rows(const StepArgs& args, int64_t f0, int nv, int lane, BatchIn& in) {
   constexpr int NL = MODE == VSS_MODE_SA ? 2 : 6;
-  in.progress = 0;
-  in.reset_prev = 0;
-  in.ctr = 0;
-  in.b = {};
-  if (fl < nv) {
-    in.progress = at(args.s.progress_buf + f0, 8u * (uint32_t)fl);
-    in.reset_prev = at(args.s.reset_buf + f0, 8u * (uint32_t)fl);
-    in.ctr = at(args.s.rng_counter + f0, 4u * (uint32_t)fl);
-    load_bodies(args.s.state, args.n, f0, fl, in.b);
-  }
-  prefetch12((MODE == VSS_MODE_FULL ? args.io.actions : args.io.ou_buf) + f0 * 12, nv, lane, in.blk);
+  prefetch12<kFpw>((MODE == VSS_MODE_FULL ? args.io.actions : args.io.ou_buf) + f0 * 12, nv, lane, in.blk);
   if constexpr (MODE != VSS_MODE_FULL) prefetch_lrn<NL>(args.io.actions + f0 * NL, nv, lane, in.lrn);
+}
+
+// Unpredicated like the rows: in a partial last wave the lanes past its last field load that field
+// again.  Such a lane runs no physics and no reset and stores nothing (`valid`, `owner`), and the
+// streams end at the wave's nv fields, so what it holds reaches no output.
+__device__ __forceinline__ int last_field(int fl, int nv) { return fl < nv ? fl : nv - 1; }
+
+__device__ __forceinline__ void load_state(const StepArgs& args, int64_t f0, int nv, int fl, BatchIn& in) {
+  const int flc = last_field(fl, nv);
+  in.progress = at(args.s.progress_buf + f0, 8u * (uint32_t)flc);
+  in.reset_prev = at(args.s.reset_buf + f0, 8u * (uint32_t)flc);
+  in.ctr = at(args.s.rng_counter + f0, 4u * (uint32_t)flc);
+  in.b = {};
+  load_bodies(args.s.state, args.n, f0, flc, in.b);
 }
 
 // The body of step_kernel<MODE, REPLAY> (VERSUS = false) and of step_versus_kernel<MODE> (VERSUS =
@@ -1012,9 +1035,10 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   static_assert(2 * kFpw == kWave, "two lanes per field");
   constexpr int kLds = 32 * kRec > kFpw * REC ? 32 * kRec : kFpw * REC;
   static_assert(kFpw * REC <= kLds, "observation records must fit the LDS block");
-  __shared__ float lds[kLds + kTabWords];
+  __shared__ float lds[kLds + kTabLds];
   uint32_t* tab = reinterpret_cast<uint32_t*>(lds + kLds);
-  stage_obs_table(tab, threadIdx.x);
+  uint32_t tabw[kTabPerLane];
+  load_obs_table(threadIdx.x, tabw);
 
   const int64_t n = args.n;
   const uint32_t pol = args.store_policy;
@@ -1028,10 +1052,12 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   const int64_t f0 = (int64_t)blockIdx.x * kFpw;
   const int nv = (int)(n - f0 < kFpw ? n - f0 : kFpw);
   BatchIn cur;
-  load_batch<MODE>(args, f0, nv, fl, lane, cur);
+  load_rows<MODE>(args, f0, nv, lane, cur);
   float2 opp[2];  // versus: the wave's (nv, 6) opponent action rows, with the other inputs
   if constexpr (VERSUS) prefetch_lrn<6>(vs.opp_actions + f0 * 6, nv, lane, opp);
   if constexpr (MIRROR) prefetch_lrn<NL>(yl.actions + f0 * NL, nv, lane, opp);  // the yellow learner's rows
+  load_state(args, f0, nv, fl, cur);
+  loads_issued();
   const int64_t f = f0 + fl;
   const bool valid = fl < nv;
   const bool owner = valid && writer;  // stores the field's outputs
@@ -1043,7 +1069,8 @@ __device__ __forceinline__ void step_body(const StepArgs& args, const vss_versus
   // -- actions: FULL reads (N,12); wrapped modes read + update the OU action buffer, then take the
   //    learner's slots (and, versus, the opponent's) --------------------------------------------------
   float a[12];
-  stage12(cur.blk, nv, lds, lane);
+  stage_obs_table(tab, lane, tabw);  // first read by coop_store_obs, behind the barriers below
+  stage12<kFpw>(cur.blk, nv, lds, lane);
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < 12; ++k) a[k] = rec[k];
@@ -1280,9 +1307,10 @@ struct RolloutArgs {
 
 __global__ __launch_bounds__(kWave) void rollout_kernel(RolloutArgs args) {
   static_assert(kFpw * kRecObs6 <= kWave * kRec, "observation records must fit the LDS block");
-  __shared__ float lds[kWave * kRec + kTabWords];
+  __shared__ float lds[kWave * kRec + kTabLds];
   uint32_t* tab = reinterpret_cast<uint32_t*>(lds + kWave * kRec);
-  stage_obs_table(tab, threadIdx.x);
+  uint32_t tabw[kTabPerLane];
+  load_obs_table(threadIdx.x, tabw);
   const int64_t n = args.n;
   const int lane = threadIdx.x;
   const int fl = lane & (kFpw - 1);  // lanes L and L + 32 hold the same field
@@ -1296,30 +1324,30 @@ __global__ __launch_bounds__(kWave) void rollout_kernel(RolloutArgs args) {
   float* rec = lds + fl * kRec;
   float* orec = lds + lane * kRecObs6;  // observation record (lanes < kFpw)
 
-  int64_t progress = 0, reset_prev = 0;
-  uint32_t ctr = 0;
-  Bodies b = {};
-  if (valid) {
-    progress = at(args.s.progress_buf + f0, 8u * (uint32_t)fl);
-    reset_prev = at(args.s.reset_buf + f0, 8u * (uint32_t)fl);
-    ctr = at(args.s.rng_counter + f0, 4u * (uint32_t)fl);
-    load_bodies(args.s.state, n, f0, fl, b);
-  }
+  // the first step's action rows ahead of the state, as in the step (load_rows)
   float4 pre[3];
-  prefetch12(args.io.actions + f0 * 12, nv, lane, pre);
+  prefetch12<kFpw>(args.io.actions + f0 * 12, nv, lane, pre);
+  const int flc = last_field(fl, nv);  // unpredicated loads, see load_state
+  int64_t progress = at(args.s.progress_buf + f0, 8u * (uint32_t)flc);
+  int64_t reset_prev = at(args.s.reset_buf + f0, 8u * (uint32_t)flc);
+  const uint32_t ctr = at(args.s.rng_counter + f0, 4u * (uint32_t)flc);
+  Bodies b = {};
+  load_bodies(args.s.state, n, f0, flc, b);
+  loads_issued();
   float dof[12];
   int64_t done = reset_prev;
   const float clip = args.p.clip_actions;
+  stage_obs_table(tab, lane, tabw);  // once: the steps' barriers order it before every stream
 
   for (int k = 0; k < args.k_steps; ++k) {
     const int64_t step_off = (int64_t)k * n;
     float a[12];
-    stage12(pre, nv, lds, lane);
+    stage12<kFpw>(pre, nv, lds, lane);
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 12; ++i) a[i] = clampf(rec[i], -clip, clip);
     __syncthreads();
-    if (k + 1 < args.k_steps) prefetch12(args.io.actions + (step_off + n + f0) * 12, nv, lane, pre);
+    if (k + 1 < args.k_steps) prefetch12<kFpw>(args.io.actions + (step_off + n + f0) * 12, nv, lane, pre);
 
     if (reset_prev != 0) progress = 0;
     float pbx = b.bx, pby = b.by, prx[6], pry[6];
@@ -1398,26 +1426,31 @@ __global__ __launch_bounds__(kWave) void reset_kernel(int64_t n, vss_params p, v
 
 template <int A>
 __global__ __launch_bounds__(kWave) void observe_kernel(int64_t n, vss_state s, float* obs) {
-  __shared__ float lds[kWave * obs_rec<A>() + kTabWords];
+  __shared__ float lds[kWave * obs_rec<A>() + kTabLds];
   uint32_t* tab = reinterpret_cast<uint32_t*>(lds + kWave * obs_rec<A>());
-  stage_obs_table(tab, threadIdx.x);
+  uint32_t tabw[kTabPerLane];
+  load_obs_table(threadIdx.x, tabw);
   const int lane = threadIdx.x;
   const int64_t f0 = (int64_t)blockIdx.x * kWave;
   const int nv = (int)(n - f0 < kWave ? n - f0 : kWave);
 
   float* rec = lds + lane * kRec;
   float* orec = lds + lane * obs_rec<A>();
-  coop_load<12>(s.dof_velocity_buf + f0 * 12, nv, lds, lane);
+  // every input in one round trip: the table, the wave's (nv, 12) dof rows (64 fields: up to 192
+  // float4, three per lane) and the state channels, before the first wait
+  float4 pre[3];
+  prefetch12<kWave>(s.dof_velocity_buf + f0 * 12, nv, lane, pre);
+  Bodies b = {};
+  load_bodies(s.state, n, f0, last_field(lane, nv), b);  // unpredicated, see load_state
+  loads_issued();
+  stage_obs_table(tab, lane, tabw);
+  stage12<kWave>(pre, nv, lds, lane);
   __syncthreads();
   float dof[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) dof[k] = rec[k];
   __syncthreads();
-  Bodies b = {};
-  if (lane < nv) {
-    load_bodies(s.state, n, f0, lane, b);
-    write_obs_record<A>(orec, b, dof);
-  }
+  if (lane < nv) write_obs_record<A>(orec, b, dof);
   wait_loads();
   __syncthreads();
   coop_store_obs<A>(obs + f0 * (52 * A), nv, lds, tab, lane);

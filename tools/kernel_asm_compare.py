@@ -5,8 +5,9 @@
 Each tree's vss_step.hip is compiled with the Makefile's STEP_FLAGS to device assembly (-S
 --offload-device-only); comments and directives are dropped and the local label numbers
 (.LBB<function>_<block>) normalised, so two kernels compare equal exactly when their instruction
-sequences are the same.  Resource usage comes from -Rpass-analysis=kernel-resource-usage.  A cross-
-compile: no GPU is needed.
+sequences are the same.  Resource usage comes from -Rpass-analysis=kernel-resource-usage, and each
+kernel gets one more line on its prologue (the loads and waits in front of its first physics
+instruction, see `prologue`).  A cross-compile: no GPU is needed.
 """
 from __future__ import annotations
 
@@ -67,10 +68,42 @@ def device_asm(tree: str):
     return {demangled[k]: v for k, v in body.items()}, fmt
 
 
+def prologue(ins):
+    """The loads and waits in front of a kernel's first physics instruction, in one line.
+
+    The prologue runs from the kernel's entry to its first v_permlane32_swap (the physics, or the OU draws
+    of the wrapped modes), or, where a kernel has none, to its first store to global memory.  Reported:
+    the `s_waitcnt vmcnt` in it, the global loads issued before the first of those waits and behind it
+    (position of the last load and of the first wait, as instruction indices), the backward branches
+    (a load -> wait -> ds_write loop is one) and the s_load batches (runs of s_load with no other
+    instruction but s_ ALU between them) with the lgkmcnt waits.
+    """
+    end = next((i for i, s in enumerate(ins) if s.startswith("v_permlane32_swap")), None)
+    if end is None:
+        end = next((i for i, s in enumerate(ins) if re.match(r"(global|buffer)_store", s)), len(ins))
+    pro = ins[:end]
+    waits = [i for i, s in enumerate(pro) if s.startswith("s_waitcnt") and "vmcnt" in s]
+    loads = [i for i, s in enumerate(pro) if s.startswith("global_load")]
+    labels = {s[:-1]: i for i, s in enumerate(pro) if s.endswith(":")}
+    back = sum(1 for i, s in enumerate(pro)
+               if s.startswith("s_cbranch") and labels.get(s.split()[-1], len(pro)) < i)
+    first = waits[0] if waits else len(pro)
+    sloads = [i for i, s in enumerate(pro) if s.startswith("s_load")]
+    batches = sum(1 for k, i in enumerate(sloads)
+                  if k == 0 or any(s.startswith("s_waitcnt") for s in pro[sloads[k - 1]:i]))
+    return (f"prologue {len(pro)} instructions: {len(waits)} vmcnt waits, {len(loads)} global loads, "
+            f"{sum(1 for i in loads if i < first)} before the first wait (at {first}), "
+            f"{sum(1 for i in loads if i > first)} behind it (last load at {loads[-1] if loads else '-'}), "
+            f"{back} backward branches, s_load in {batches} batches")
+
+
 def main(argv):
     parent, tree = argv[1], argv[2] if len(argv) > 2 else REPO
     pa, pr = device_asm(parent)
     ta, tr = device_asm(tree)
+    for asm, res in ((pa, pr), (ta, tr)):
+        for k in res:
+            res[k] += "\n             " + prologue(asm[k])
     new = [k for k in ta if k not in pa]
     gone = [k for k in pa if k not in ta]
     print("gfx950 assembly of vss_step.hip per kernel symbol, parent commit against this tree.")
